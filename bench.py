@@ -12,10 +12,14 @@ Rank 0 prints ONE JSON line.
 Workload (config.workload): one 3840x2160 I420 stream per GPU, planes resident in HBM when the timed region starts; SURVEY.md section
 8d's synthetic clip (tests/clipgen.py: 600 distinct camera poses -- smooth pan + AR(1) jitter in translation / rotation / zoom --, a scene
 cut at frame 300, ground-truth homographies and the jitter-free render); OBS "Homography" preset (tracking 480x270, 2x1 regions, 2x2
-mesh), predictive_samples = 10, auto-crop 5 %.  Beside `value`: latency (always >= 500 synchronised pushes), the live roofline of the remap
-(always >= 64 HIP-event samples inside / right after the timed region), the PCIe-inclusive rate, the picture quality against the ideal
-render for the GPU and for the CPU oracle, the oracle timed on the host cores, the reference's own remap kernel (compiled for this chip)
-timed on the same frame, short legs of the other BASELINE configurations, and K concurrent streams on this one GPU.
+mesh), predictive_samples = 10, auto-crop 5 %.
+
+A plain run sets up, fills the pipeline, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step` and what the run
+was).  `--full` adds, beside `value`: latency (always >= 500 synchronised pushes), the live roofline of the remap (always >= 64 HIP-event
+samples inside / right after the timed region), the PCIe-inclusive rate, the picture quality against the ideal render for the GPU and for the
+CPU oracle, the oracle timed on the host cores, the reference's own remap kernel (compiled for this chip) timed on the same frame, short legs
+of the other BASELINE configurations, and K concurrent streams on this one GPU.  `--dump-outputs DIR` writes the frames of the last timed step
+(bench.dump_outputs), so that two builds can be compared output for output: the clip and the settings are fixed by the arguments.
 
 `--gpus N` with N > 1 launched plainly (no torch.distributed.run around it) spawns its N ranks itself; whichever way it was launched, the
 line's `n_gpus` is the number of ranks that timed, and the run fails (exit code 3) when that is not --gpus."""
@@ -141,27 +145,35 @@ def parse():
     ap.add_argument("--cols", type=int, default=3840)
     ap.add_argument("--preset", default="homography", choices=["homography", "field"])
     ap.add_argument("--pool", type=int, default=600, help="distinct source frames (camera poses) kept in HBM; scene cut at pool / 2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
     ap.add_argument("--format", default="i420", choices=["i420", "nv12", "packed"],
                     help="frame format resident in HBM: 4:2:0 planes in and out (BASELINE metric) or the packed 8UC3 boundary format")
     ap.add_argument("--lens", default="off", choices=["off", "fused", "two-pass"],
                     help="BASELINE config 5: lens-correction pre-warp (profile of SURVEY.md section 8d) fused into the stabilizing remap, "
                          "or as the reference chain's separate LC pass (two-pass; --format packed only)")
-    ap.add_argument("--no-lookahead", action="store_true", help="skip the extra pass in which every frame is announced one push ahead")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the extra (untimed-for-`value`) pass with host-resident frames")
+    ap.add_argument("--no-lookahead", action="store_true", help="--full: skip the extra pass in which every frame is announced one push ahead")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the extra (untimed-for-`value`) pass with host-resident frames")
     ap.add_argument("--no-overlap", action="store_true", help="keep the output remap on the tracking stream")
-    ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU work of the oracle baseline")
-    ap.add_argument("--quality-frames", type=int, default=90, help="frames of the picture-quality pass (GPU and oracle vs the ideal render); 0 = skip")
+    ap.add_argument("--cpu-budget", type=float, default=10.0, help="--full: seconds of CPU work of the oracle baseline")
+    ap.add_argument("--quality-frames", type=int, default=90, help="--full: frames of the picture-quality pass (GPU and oracle vs the ideal render); 0 = skip")
     ap.add_argument("--streams-per-gpu", type=int, default=1,
                     help="K independent streams (filters, HIP streams, clips, host threads) on every GPU: `value` is the aggregate over all of them. "
                          "One 4K60 stream occupies < 1 %% of the GPU -- streams per device is the scaling that matters to a deployment")
     ap.add_argument("--input", default=None, help="raw 4:2:0 file (I420, or NV12 with --format nv12) of --cols x --rows frames instead of the synthetic clip "
                                                   "(the reference's harness reads a clip: Modules/VideoEditor/VideoProcessor.cpp:148-230)")
     ap.add_argument("--write-input", default=None, help="write the first --pool frames of the synthetic clip to this file (raw I420 / NV12) and exit")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short legs of the other BASELINE configurations (1080p, lens-fused, field preset)")
-    ap.add_argument("--no-reference-kernel", action="store_true", help="skip timing the reference's compiled remap kernel (oracle/_ref) on the same frame")
-    ap.add_argument("--no-multi-stream", action="store_true", help="skip the extra leg with 4 concurrent streams on this GPU")
-    ap.add_argument("--no-sensors", action="store_true", help="do not sample the GPU's clock / power sensors (sysfs) during the timed regions")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the short legs of the other BASELINE configurations (1080p, lens-fused, field preset)")
+    ap.add_argument("--no-reference-kernel", action="store_true", help="--full: skip timing the reference's compiled remap kernel (oracle/_ref) on the same frame")
+    ap.add_argument("--no-multi-stream", action="store_true", help="--full: skip the extra leg with 4 concurrent streams on this GPU")
+    ap.add_argument("--no-sensors", action="store_true", help="--full: do not sample the GPU's clock / power sensors (sysfs) during the timed regions")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the line reports: sustained rate, latency passes, sensors, per-stage and roofline figures, "
+                         "look-ahead, standalone and reference kernels, PCIe-inclusive rate, other configurations, concurrent streams, CPU baseline, picture "
+                         "quality, the N > 1 shared-resource legs (the --no-* switches select among these).  Without it the run sets up, warms up, "
+                         "times --steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the stabilized frames of the last timed step (rank 0, stream 0) to DIR/<plane>.npy as float32: "
+                         "a fixed, seeded sample of each plane's pixels, the same positions in every frame, <= 48 MiB in all")
     return ap.parse_args()
 
 
@@ -317,10 +329,11 @@ def quality_pass(lvk, ctx, oracle, clip, preset_name, nframes, nthreads):
 class Rig:
     """One stream: a context on a HIP stream of its own, a filter, its frames resident in HBM, and step() = one push in steady state."""
 
-    def __init__(self, lvk, local_rank, device, seed, rows, cols, preset, fmt, lens, overlap, pool, input_path=None, cut=True, pingpong=False):
+    def __init__(self, lvk, local_rank, device, seed, rows, cols, preset, fmt, lens, overlap, pool, input_path=None, cut=True, pingpong=False, n_out=4):
         import torch
         from tests import clipgen
         self.lvk, self.rows, self.cols, self.fmt, self.lens, self.preset, self.seed = lvk, rows, cols, fmt, lens, preset, seed
+        self.n_out = max(4, n_out)           # output buffers, used round robin: push i writes outs[i % n_out]
         # the filter works on its own (non-blocking) stream: the process default stream would implicitly serialise with every
         # blocking stream of the process
         self.stream = torch.cuda.Stream(device)
@@ -368,7 +381,7 @@ class Rig:
         if self.yuv420:
             self.planes = planes
             self.frames = None
-            self.outs = [tuple(torch.empty_like(q) for q in planes[0]) for _ in range(4)]
+            self.outs = [tuple(torch.empty_like(q) for q in planes[0]) for _ in range(self.n_out)]
             self.planes_args = [self.filt.prepare_yuv420(q) for q in planes]          # addresses / pitches marshalled once, outside the timed region
             self.outs_args = [self.filt.prepare_yuv420(o) for o in self.outs]
         elif self.obs_fmt is not None:
@@ -383,12 +396,12 @@ class Rig:
                 self.ctx.egress_obs(self.obs_fmt, self.clip.render444(i), pl)
                 self.obs_planes.append(pl)
             self.ctx.sync()
-            self.outs = [[torch.empty(sh, dtype=torch.uint8, device=device) for sh in shapes()] for _ in range(4)]
+            self.outs = [[torch.empty(sh, dtype=torch.uint8, device=device) for sh in shapes()] for _ in range(self.n_out)]
             self.planes_args = [self.filt.prepare_obs(self.obs_fmt, q) for q in self.obs_planes]
             self.outs_args = [self.filt.prepare_obs(self.obs_fmt, o) for o in self.outs]
         else:
             self.frames = [self.clip.render444(i) for i in range(pool)]
-            self.outs = [torch.empty_like(self.frames[0]) for _ in range(4)]
+            self.outs = [torch.empty_like(self.frames[0]) for _ in range(self.n_out)]
         if self.lens_map is not None:
             self.lens_bufs = [torch.empty_like(self.frames[0]) for _ in range(self.delay + 4)]       # corrected frames stay borrowed for `delay` pushes
         torch.cuda.synchronize()
@@ -421,13 +434,13 @@ class Rig:
         if self.yuv420:
             if announce:                # the next frame is resident already: lvk_hip_stab_prefetch_yuv420, then the push of this one
                 self.filt.prefetch_yuv420_prepared(self.planes_args[self.index(i + 1)])
-            return self.filt.apply_yuv420_prepared(self.planes_args[k], i, self.outs_args[i & 3])
+            return self.filt.apply_yuv420_prepared(self.planes_args[k], i, self.outs_args[i % self.n_out])
         if self.obs_fmt is not None:
-            return self.filt.apply_obs_prepared(self.planes_args[k], i, self.outs_args[i & 3])
+            return self.filt.apply_obs_prepared(self.planes_args[k], i, self.outs_args[i % self.n_out])
         if self.lens_map is not None:
             corrected = self.ctx.remap_map(self.frames[k], self.lens_map, bg=(0, 0, 0), out=self.lens_bufs[i % len(self.lens_bufs)])     # LCFilter::filter
-            return self.filt.apply(corrected, timestamp=i, out=self.outs[i & 3])
-        return self.filt.apply(self.frames[k], timestamp=i, out=self.outs[i & 3])
+            return self.filt.apply(corrected, timestamp=i, out=self.outs[i % self.n_out])
+        return self.filt.apply(self.frames[k], timestamp=i, out=self.outs[i % self.n_out])
 
     def sync(self):
         self.ctx.sync()                      # lvk_hip_sync: every stream of the filter (tracking, bulk, transfers)
@@ -780,6 +793,35 @@ def reference_kernel_leg(rig):
             "product_hbm_frac": b / (t_hip * 1e-6) / 1e9 / HBM_PEAK_GBS, "speedup": t_ref / t_hip, "outputs_bit_equal": same}
 
 
+DUMP_BYTES = 48 << 20                 # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SEED = 0x4C564B44
+
+
+def dump_outputs(rig, n, out_dir):
+    """--dump-outputs: the frames that the last n pushes of `rig` (the last timed step) emitted into its output buffers, as the caller receives
+    them, written as out_dir/<plane>.npy, float32 arrays of shape (n, samples).  A plane larger than its share of DUMP_BYTES is sampled at
+    positions drawn once from DUMP_SEED, the same positions in every frame, so that two runs of the same command write the same files.  The
+    caller has synchronised the rig (run_region ends with a device-wide synchronisation)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    pushes = range(rig.step_no - n, rig.step_no)
+    frames = [rig.outs[i % rig.n_out] for i in pushes]
+    frames = [tuple(f) if isinstance(f, (tuple, list)) else (f,) for f in frames]
+    names = {"i420": ("y", "u", "v"), "nv12": ("y", "uv"), "packed": ("yuv444",)}.get(rig.fmt) or tuple(f"plane{k}" for k in range(len(frames[0])))
+    sizes = [q.numel() for q in frames[0]]
+    frac = min(1.0, DUMP_BYTES / 4 / (n * sum(sizes)))
+    rng = np.random.default_rng(DUMP_SEED)
+    written = {}
+    for k, (name, size) in enumerate(zip(names, sizes)):
+        m = size if frac >= 1.0 else max(1, int(size * frac))
+        idx = None if m == size else torch.from_numpy(np.sort(rng.choice(size, m, replace=False))).to(frames[0][k].device)
+        rows = [(f[k].reshape(-1) if idx is None else f[k].reshape(-1)[idx]).to(torch.float32) for f in frames]
+        arr = torch.stack(rows).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+    return written
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -813,8 +855,10 @@ def main():
     rows, cols = args.rows, args.cols
     seed0 = 0x4C564B31 + rank * K
     pool_k = args.pool if K == 1 else max(48, min(args.pool, 600 // K))      # K clips share the HBM budget of one
+    # --dump-outputs: one output buffer per push of a step, so that every frame of the last timed step is still there to be written
+    n_out = max(1, args.frames_per_step) if args.dump_outputs else 4
     rigs = [Rig(lvk, local_rank, device, seed0 + k, rows, cols, args.preset, args.format, args.lens, not args.no_overlap,
-                pool_k, input_path=args.input) for k in range(K)]
+                pool_k, input_path=args.input, n_out=n_out) for k in range(K)]
     rig = rigs[0]
     filt, ctx, clip, delay, pool = rig.filt, rig.ctx, rig.clip, rig.delay, rig.pool
     settings, lens_params = rig.settings, rig.lens_params
@@ -836,7 +880,7 @@ def main():
     # the sensor sampler (a separate process) is started BEFORE the warmup, so that nothing but the barrier sits between the warmup steps
     # and the timed region (its start-up wait used to idle the GPU for 0.3 s right in front of the timed pushes)
     sampler = None
-    if rank == 0 and not args.no_sensors:
+    if args.full and rank == 0 and not args.no_sensors:
         try:
             props = torch.cuda.get_device_properties(local_rank)
             bus = "%04x:%02x:%02x" % (getattr(props, "pci_domain_id", 0), props.pci_bus_id, props.pci_device_id) if hasattr(props, "pci_bus_id") else None
@@ -864,9 +908,10 @@ def main():
             step()
     else:
         run_region(rigs, n_warm, lambda: None, local_rank)
-    # live HIP-event timing of the dominant kernel inside the timed region: that stage only, and one launch in eight (an event pair per
+    # --full: live HIP-event timing of the dominant kernel inside the timed region: that stage only, and one launch in eight (an event pair per
     # frame is two host API calls in the per-frame turnaround -- the measurement would slow what it measures by ~4 %)
-    filt.set_profiling(True, stages=("remap",), every=8)
+    if args.full:
+        filt.set_profiling(True, stages=("remap",), every=8)
 
     def device_sync():
         for r in rigs:
@@ -881,10 +926,71 @@ def main():
 
     barrier()
     schedule = {}
-    filt.schedule_counters(reset=True)
+    if args.full:
+        filt.schedule_counters(reset=True)
     wall0 = time.time()
     elapsed, emitted, stamps = run_region(rigs, n_timed, device_sync, local_rank)
     wall1 = time.time()
+    dumped = dump_outputs(rig, fps_, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
+    rank_report = {"rank": rank, "device": local_rank, "clip_seed": seed0, "streams": K, "frames": emitted, "elapsed_s": elapsed, "frames_per_s": emitted / elapsed,
+                   "numa_cpus": (f"{numa_cpus[0]}-{numa_cpus[-1]} ({len(numa_cpus)})" if numa_cpus else "unbound")}
+
+    def headline(elapsed_max, total_frames, n_ranks):
+        """The keys every run prints: the timed region's rate and what it ran."""
+        return {
+            "metric": ("stabilized frames/sec (one 4K YUV420 stream per GPU, steady state)" if K == 1 else f"stabilized frames/sec ({K} concurrent 4K YUV420 streams per GPU, steady state)") if yuv420 else
+                      "stabilized frames/sec (one 4K packed-YUV444 stream per GPU, steady state)",
+            "value": total_frames / elapsed_max,
+            "unit": "frames/s",
+            "n_gpus": n_ranks,                               # the ranks that timed
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed_max / args.steps * 1e3,          # one step = frames_per_step consecutive frames (config.frames_per_step)
+            "ms_per_frame": elapsed_max / n_timed * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic" if args.input is None else f"file {os.path.basename(args.input)} ({pool} frames resident in HBM, cycled)",
+            "config": {"workload": (f"{cols}x{rows} {args.format.upper()} (YUV 4:2:0) stream per GPU, planes resident in HBM, ingest -> lvk::StabilizationFilter -> egress, "
+                                    if yuv420 else f"{cols}x{rows} packed YUV444 8UC3 stream per GPU (lvk::StabilizationFilter boundary format), ")
+                                   + f"OBS '{args.preset}' preset, tracking 480x270, predictive_samples={delay}, crop 5%"
+                                   + ("" if args.lens == "off" else f", lens correction {args.lens} (fx=fy=0.8W, k1=-0.12, k2=0.03)")
+                                   + ("" if K == 1 else f"; {K} such streams per GPU, one host thread each"),
+                       "clip": (f"SURVEY 8d generator: {pool} distinct poses (smooth pan + AR(1) jitter: 0.4 % W translation, 0.15 deg, 0.2 % zoom), scene cut at frame {pool // 2}, "
+                                f"cycled; rendered on the GPU in {t_gen:.1f} s") if args.input is None else f"{args.input}: {pool} frames, cycled",
+                       "parallelism": f"{n_ranks} rank(s), one per GPU, {K} independent stream(s) each, no collective (gloo barrier only)",
+                       "streams_per_gpu": K, "frames_in_hbm": pool * K, "host_cpus_bound": len(numa_cpus),
+                       "frames_per_step": fps_,
+                       "step": f"one step = one batch of {fps_} consecutive frames of the stream = {fps_} pushes (lvk_hip_stab_push_yuv420), each emitting one stabilized frame; "
+                               f"the timed region is exactly {args.steps} steps = {n_timed} pushes per stream",
+                       "pipeline_fill": f"{n_fill} untimed pushes (frame delay, the detector's start-up burst, ~0.1 s for the chip's clock ramp) before the {args.warmup} warmup steps"},
+            "full": bool(args.full),
+            "dump_outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None,
+        }
+
+    def finish(result, n_ranks):
+        rc = 0
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+            if n_ranks != args.gpus:
+                sys.stderr.write(f"bench.py: --gpus {args.gpus} but {n_ranks} rank(s) reported\n")
+                rc = 3
+        for r in rigs:
+            r.close()
+        if world > 1:
+            dist.destroy_process_group()
+        if rc:
+            raise SystemExit(rc)
+        return result
+
+    if not args.full:
+        # a plain run: the timed steps are all it measures
+        elapsed_max, total_frames = lvk.shard.reduce_timing(elapsed, emitted)
+        rank_reports = lvk.shard.gather_rank_reports(rank_report)
+        result = dict(headline(elapsed_max, total_frames, len(rank_reports)), ranks=rank_reports) if rank == 0 else None
+        return finish(result, len(rank_reports))
+
     schedule["timed_region"] = filt.schedule_counters(reset=True)
     free_running = np.diff(np.array(stamps)) * 1e3          # host time per push of stream 0 in the free-running timed region
     barrier()
@@ -902,7 +1008,7 @@ def main():
     filt.set_profiling(False)
     stats = filt.stats()
     import zlib
-    last_out = rig.outs[(rig.step_no - 1) & 3]
+    last_out = rig.outs[(rig.step_no - 1) % rig.n_out]
     out_crc = 0
     for q in (last_out if isinstance(last_out, tuple) else (last_out,)):
         out_crc = zlib.crc32(q.cpu().numpy().tobytes(), out_crc)
@@ -1035,17 +1141,15 @@ def main():
 
     elapsed_max, total_frames = lvk.shard.reduce_timing(elapsed, emitted)
     sustained_max, sustained_frames = lvk.shard.reduce_timing(sustained_s, sustained_emitted)
-    rank_reports = lvk.shard.gather_rank_reports({
-        "rank": rank, "device": local_rank, "clip_seed": seed0, "streams": K, "frames": emitted, "elapsed_s": elapsed, "frames_per_s": emitted / elapsed,
-        "sustained_frames_per_s": sustained_emitted / sustained_s, "link": gpu_link_info(local_rank), "numa_cpus": (f"{numa_cpus[0]}-{numa_cpus[-1]} ({len(numa_cpus)})" if numa_cpus else "unbound"),
+    rank_reports = lvk.shard.gather_rank_reports(dict(
+        rank_report, sustained_frames_per_s=sustained_emitted / sustained_s, link=gpu_link_info(local_rank),
         # every rank reports the latency of every stream it ran (north star: throughput AND p99 at 1 / 2 / 4 / 8 GPUs): p50 / p99 per stream,
         # and the rank's own figure = its slowest stream
-        "latency_ms": {"p50": max(float(np.percentile(x, 50)) for x in lats), "p99": max(float(np.percentile(x, 99)) for x in lats),
-                       "max": max(float(np.max(x)) for x in lats), "samples": len(lats[0])},
-        "stream_latency_ms": [dict(percentiles(x), samples=len(x)) for x in lats]})
+        latency_ms={"p50": max(float(np.percentile(x, 50)) for x in lats), "p99": max(float(np.percentile(x, 99)) for x in lats),
+                    "max": max(float(np.max(x)) for x in lats), "samples": len(lats[0])},
+        stream_latency_ms=[dict(percentiles(x), samples=len(x)) for x in lats]))
 
     result = None
-    rc = 0
     if rank == 0:
         remap_ms, remap_n = prof["remap"]
         remap_s = remap_ms / remap_n * 1e-3 if remap_n else None
@@ -1099,40 +1203,15 @@ def main():
                                             "profiles/r06_kernel_stats.csv are 5.9 us for the downscale = 18 %, 9.5 us for the conversion = 49 %)"})
         n_ranks = len(rank_reports)
         legs_agg = aggregate_legs(leg_reports) if leg_reports else None
-        result = {
-            "metric": ("stabilized frames/sec (one 4K YUV420 stream per GPU, steady state)" if K == 1 else f"stabilized frames/sec ({K} concurrent 4K YUV420 streams per GPU, steady state)") if yuv420 else
-                      "stabilized frames/sec (one 4K packed-YUV444 stream per GPU, steady state)",
-            "value": total_frames / elapsed_max,
-            "unit": "frames/s",
-            "n_gpus": n_ranks,                               # the ranks that timed
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed_max / args.steps * 1e3,          # one step = frames_per_step consecutive frames (config.frames_per_step)
-            "ms_per_frame": elapsed_max / n_timed * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic" if args.input is None else f"file {os.path.basename(args.input)} ({pool} frames resident in HBM, cycled)",
-            "config": {"workload": (f"{cols}x{rows} {args.format.upper()} (YUV 4:2:0) stream per GPU, planes resident in HBM, ingest -> lvk::StabilizationFilter -> egress, "
-                                    if yuv420 else f"{cols}x{rows} packed YUV444 8UC3 stream per GPU (lvk::StabilizationFilter boundary format), ")
-                                   + f"OBS '{args.preset}' preset, tracking 480x270, predictive_samples={delay}, crop 5%"
-                                   + ("" if args.lens == "off" else f", lens correction {args.lens} (fx=fy=0.8W, k1=-0.12, k2=0.03)")
-                                   + ("" if K == 1 else f"; {K} such streams per GPU, one host thread each"),
-                       "clip": (f"SURVEY 8d generator: {pool} distinct poses (smooth pan + AR(1) jitter: 0.4 % W translation, 0.15 deg, 0.2 % zoom), scene cut at frame {pool // 2}, "
-                                f"cycled; rendered on the GPU in {t_gen:.1f} s") if args.input is None else f"{args.input}: {pool} frames, cycled",
-                       "parallelism": f"{n_ranks} rank(s), one per GPU, {K} independent stream(s) each, no collective (gloo barrier only)",
-                       "streams_per_gpu": K, "frames_in_hbm": pool * K, "host_cpus_bound": len(numa_cpus),
-                       "frames_per_step": fps_,
-                       "step": f"one step = one batch of {fps_} consecutive frames of the stream = {fps_} pushes (lvk_hip_stab_push_yuv420), each emitting one stabilized frame; "
-                               f"the timed region is exactly {args.steps} steps = {n_timed} pushes per stream",
-                       "pipeline_fill": f"{n_fill} untimed pushes (frame delay, the detector's start-up burst, ~0.1 s for the chip's clock ramp) before the {args.warmup} warmup steps",
+        result = headline(elapsed_max, total_frames, n_ranks)
+        result["config"].update({
                        # copies of the line's steady-state figures (>= 600 frames, p50 / p99 of a synchronised push) where a parser that keeps
                        # only the contract's keys still finds them
                        "steady_state": {"frames_per_s": sustained_frames / sustained_max, "frames": int(sustained_frames),
                                         "p50_ms": max(r["latency_ms"]["p50"] for r in rank_reports), "p99_ms": max(r["latency_ms"]["p99"] for r in rank_reports)},
                        "shared_resource_legs": ({k: ({kk: v[kk] for kk in ("value", "p50_ms", "p99_ms", "per_rank_frames_per_s") if kk in v} if isinstance(v, dict) else v)
-                                                 for k, v in legs_agg.items() if k != "ranks"} if legs_agg else None)},
+                                                 for k, v in legs_agg.items() if k != "ranks"} if legs_agg else None)})
+        result.update({
             # SURVEY 8d's metric as it is defined (steady state, >= 600 frames; p50 / p99 of one synchronised push) beside the contract's `value`
             "value_sustained": sustained_frames / sustained_max, "p50_ms": max(r["latency_ms"]["p50"] for r in rank_reports),
             "p99_ms": max(r["latency_ms"]["p99"] for r in rank_reports),
@@ -1199,7 +1278,7 @@ def main():
             "configs": configs,
             "multi_stream": multi_stream,
             "multi_stream_field": multi_stream_field,
-        }
+        })
         if world == 1 and K == 1 and not args.no_cpu_baseline:
             from tests import oracle_lib
             oracle = oracle_lib.load()
@@ -1229,17 +1308,7 @@ def main():
                     result["quality"] = quality_pass(lvk, ctx, oracle, clip, args.preset, max(args.quality_frames, 4 * delay + 2), nthreads)
                 except Exception as e:
                     result["quality"] = {"error": repr(e)}
-        print(json.dumps(result), flush=True)
-        if n_ranks != args.gpus:
-            sys.stderr.write(f"bench.py: --gpus {args.gpus} but {n_ranks} rank(s) reported\n")
-            rc = 3
-    for r in rigs:
-        r.close()
-    if world > 1:
-        dist.destroy_process_group()
-    if rc:
-        raise SystemExit(rc)
-    return result
+    return finish(result, len(rank_reports))
 
 
 if __name__ == "__main__":

@@ -15,10 +15,10 @@ except Exception as e:
     print(n, "FAILED", e)
 PY
 }
-run default
-run nv12 --format nv12 --no-cpu-baseline --no-pcie
-run packed --format packed --no-cpu-baseline --no-pcie
-run lensfused --lens fused --no-cpu-baseline --no-pcie
-run field --preset field --no-cpu-baseline --no-pcie
-run 1080p --rows 1080 --cols 1920 --no-cpu-baseline --no-pcie
-run noov --no-overlap --no-cpu-baseline --no-pcie
+run default --full
+run nv12 --full --format nv12 --no-cpu-baseline --no-pcie
+run packed --full --format packed --no-cpu-baseline --no-pcie
+run lensfused --full --lens fused --no-cpu-baseline --no-pcie
+run field --full --preset field --no-cpu-baseline --no-pcie
+run 1080p --full --rows 1080 --cols 1920 --no-cpu-baseline --no-pcie
+run noov --full --no-overlap --no-cpu-baseline --no-pcie

@@ -8,8 +8,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/${TAG}_check; mkdir -p $O/profiles
 timeout 1800 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log; tail -4 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err; echo "bench (driver style) rc=$?"
-python bench.py > $O/bench_default.json 2>> $O/bench.err; echo "bench (defaults) rc=$?"
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err; echo "bench (driver style) rc=$?"
+python bench.py --full > $O/bench_default.json 2>> $O/bench.err; echo "bench (defaults) rc=$?"
 python - <<PY
 import json
 for name in ("bench_driver_style", "bench_default"):
