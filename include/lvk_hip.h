@@ -311,7 +311,14 @@ int  lvk_hip_stab_push_yuv420(lvk_hip_stab* stab, const void* d_y, int y_step, c
  * o_steps / o_rows the planes of the emitted frame and their row capacity): I420 / I40A / NV12 take lvk_hip_stab_push_yuv420's route; the other formats
  * are converted into the filter's frame pool (FrameIngest::to_ocl), pushed, and the emitted frame -- the DELAYED one, at its own size -- converted back
  * (::to_obs).  Input planes consumed when the call returns; output planes complete after lvk_hip_sync(); planes that cannot hold the emitted frame are
- * refused before anything changes.  Shares the frame queue with lvk_hip_stab_push_yuv420. */
+ * refused before anything changes.  Shares the frame queue with lvk_hip_stab_push_yuv420.
+ * FORMAT CLASS (declared deviation): the emitted frame leaves in the video format of the push that emits it, which converts it only within its format
+ * class (the YUV formats, which all queue the same packed frame).  A push whose delayed frame is of the other class (BGR3 / BGRA / BGRX / RGBA frames
+ * queued and a YUV push, or the reverse -- lvk_hip_stab_next_output reports the delayed frame's format) is refused with LVK_HIP_ERR_ARG before anything
+ * changes, by this call and by lvk_hip_stab_push_yuv420 alike; lvk_hip_stab_restart() lets the new format through.  The reference converts the delayed
+ * frame into its own OBS frame (OBSFrame::to_obs_frame, viewAsFormat); this call takes one format per push and does not convert between BGR / RGB and YUV.
+ * Planes that FrameIngest::to_ocl could not read (a NULL plane, a short step, an odd width where the format subsamples, rows or cols <= 0) are likewise
+ * refused before anything changes. */
 int  lvk_hip_stab_push_obs(lvk_hip_stab* stab, int video_format, const void* const d_planes[3], const int steps[3], int rows, int cols, uint64_t timestamp,
                            void* const o_planes[3], const int o_steps[3], int o_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
 

@@ -526,11 +526,53 @@ int lvk_launch_egress_yuv420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d
 
 static inline bool aligned_to(const void* p, int step, unsigned a) { return ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)step) & (a - 1)) == 0; }
 
+// What FrameIngest::to_ocl needs of the planes of one frame of `video_format`: the planes it reads, their pitches, the parity of the size.  One
+// helper for the launcher below and for the top of lvk_hip_stab_push_obs / _yuv420, which must refuse such a frame before the filter changes.
+int lvk_ingest_obs_check(lvk_hip_ctx* ctx, int video_format, const void* const d_planes[3], const int steps[3], int rows, int cols)
+{
+    LVK_HIP_REQUIRE(ctx, d_planes && steps && d_planes[0] && rows > 0 && cols > 0);
+    const bool p1 = d_planes[1] != nullptr, p2 = d_planes[2] != nullptr;
+    switch (video_format)
+    {
+    case LVK_VIDEO_FORMAT_I420: case LVK_VIDEO_FORMAT_I40A:
+        LVK_HIP_REQUIRE(ctx, p1 && p2 && (rows & 1) == 0 && (cols & 1) == 0 && steps[0] >= cols && steps[1] >= cols / 2 && steps[2] >= cols / 2);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_NV12:
+        LVK_HIP_REQUIRE(ctx, p1 && (rows & 1) == 0 && (cols & 1) == 0 && steps[0] >= cols && steps[1] >= cols);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A:
+        LVK_HIP_REQUIRE(ctx, p1 && p2 && (cols & 1) == 0 && steps[0] >= cols && steps[1] >= cols / 2 && steps[2] >= cols / 2);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: case LVK_VIDEO_FORMAT_UYVY:
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA:
+        LVK_HIP_REQUIRE(ctx, p1 && p2 && steps[0] >= cols && steps[1] >= cols && steps[2] >= cols);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_AYUV:
+        LVK_HIP_REQUIRE(ctx, steps[0] >= 4 * cols);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_Y800:
+        LVK_HIP_REQUIRE(ctx, steps[0] >= cols);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_BGR3:
+        LVK_HIP_REQUIRE(ctx, steps[0] >= 3 * cols);
+        return LVK_HIP_OK;
+    case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX:
+        // DirectIngest::to_ocl as written (FrameIngest.cpp:743-747): rows * cols * 3 BYTES of the tightly packed 4-byte pixels, viewed as 3-byte pixels
+        LVK_HIP_REQUIRE(ctx, steps[0] == 4 * cols);
+        return LVK_HIP_OK;
+    default:
+        return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_ingest_obs: video format " + std::to_string(video_format) + " is not one FrameIngest::Select knows");
+    }
+}
+
 // FrameIngest::Select's switch (FrameIngest.cpp:36-75) as one pair of launchers.  video_format = libobs' enum video_format (LVK_VIDEO_FORMAT_*).
 int lvk_launch_ingest_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format, const void* const d_planes[3], const int steps[3],
                           int rows, int cols, void* d_dst, int dst_step)
 {
-    LVK_HIP_REQUIRE(ctx, d_planes && steps && d_planes[0] && d_dst && rows > 0 && cols > 0);
+    { const int rc = lvk_ingest_obs_check(ctx, video_format, d_planes, steps, rows, cols); if (rc != LVK_HIP_OK) return rc; }
+    LVK_HIP_REQUIRE(ctx, d_dst && dst_step >= (video_format == LVK_VIDEO_FORMAT_Y800 ? cols : 3 * cols));
     const uint8_t* p0 = (const uint8_t*)d_planes[0]; const uint8_t* p1 = (const uint8_t*)d_planes[1]; const uint8_t* p2 = (const uint8_t*)d_planes[2];
     const int fast = ((reinterpret_cast<uintptr_t>(d_dst) | (uintptr_t)dst_step) & 3u) == 0 ? 1 : 0;
     const dim3 block(64, 4), grid((cols + 255) / 256, (rows + 3) / 4);
@@ -541,14 +583,12 @@ int lvk_launch_ingest_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format
     case LVK_VIDEO_FORMAT_NV12:
         return lvk_launch_ingest_yuv420(ctx, stream, p0, steps[0], p1, steps[1], nullptr, 0, 1, rows, cols, d_dst, dst_step);
     case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A:
-        LVK_HIP_REQUIRE(ctx, p1 && p2 && (cols & 1) == 0 && steps[0] >= cols && steps[1] >= cols / 2 && steps[2] >= cols / 2 && dst_step >= 3 * cols);
         if (fast && cols % 4 == 0 && cols >= 8 && aligned_to(p0, steps[0], 4))
             hipLaunchKernelGGL(k_ingest_422_dw<0>, grid, block, 0, stream, p0, steps[0], p1, steps[1], p2, steps[2], rows, cols, (uint8_t*)d_dst, dst_step);
         else
             hipLaunchKernelGGL(k_ingest_422<0>, grid, block, 0, stream, p0, steps[0], p1, steps[1], p2, steps[2], rows, cols, (uint8_t*)d_dst, dst_step, fast);
         break;
     case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: case LVK_VIDEO_FORMAT_UYVY:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols && dst_step >= 3 * cols);
         if (fast && cols % 4 == 0 && aligned_to(p0, steps[0], 4))
         {
             if (video_format == LVK_VIDEO_FORMAT_YUY2) hipLaunchKernelGGL(k_ingest_422_dw<1>, grid, block, 0, stream, p0, steps[0], p0, 0, p0, 0, rows, cols, (uint8_t*)d_dst, dst_step);
@@ -560,30 +600,25 @@ int lvk_launch_ingest_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format
         else hipLaunchKernelGGL(k_ingest_422<3>, grid, block, 0, stream, p0, steps[0], p0, 0, p0, 0, rows, cols, (uint8_t*)d_dst, dst_step, fast);
         break;
     case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA:
-        LVK_HIP_REQUIRE(ctx, p1 && p2 && steps[0] >= cols && steps[1] >= cols && steps[2] >= cols && dst_step >= 3 * cols);
         if (fast && cols % 4 == 0 && aligned_to(p0, steps[0], 4) && aligned_to(p1, steps[1], 4) && aligned_to(p2, steps[2], 4))
             hipLaunchKernelGGL(k_ingest_444_dw<0>, grid, block, 0, stream, p0, steps[0], p1, steps[1], p2, steps[2], rows, cols, (uint8_t*)d_dst, dst_step);
         else
             hipLaunchKernelGGL(k_ingest_444<0>, grid, block, 0, stream, p0, steps[0], p1, steps[1], p2, steps[2], rows, cols, (uint8_t*)d_dst, dst_step, fast);
         break;
     case LVK_VIDEO_FORMAT_AYUV:
-        LVK_HIP_REQUIRE(ctx, steps[0] >= 4 * cols && dst_step >= 3 * cols);
         if (fast && cols % 4 == 0 && aligned_to(p0, steps[0], 16))
             hipLaunchKernelGGL(k_ingest_444_dw<1>, grid, block, 0, stream, p0, steps[0], p0, 0, p0, 0, rows, cols, (uint8_t*)d_dst, dst_step);
         else
             hipLaunchKernelGGL(k_ingest_444<1>, grid, block, 0, stream, p0, steps[0], p0, 0, p0, 0, rows, cols, (uint8_t*)d_dst, dst_step, fast);
         break;
     case LVK_VIDEO_FORMAT_Y800:                                   // DirectIngest: upload_planes(src, 1).copyTo(dst)
-        LVK_HIP_REQUIRE(ctx, steps[0] >= cols && dst_step >= cols);
         LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(d_dst, (size_t)dst_step, p0, (size_t)steps[0], (size_t)cols, (size_t)rows, hipMemcpyDeviceToDevice, stream));
         return LVK_HIP_OK;
     case LVK_VIDEO_FORMAT_BGR3:
-        LVK_HIP_REQUIRE(ctx, steps[0] >= 3 * cols && dst_step >= 3 * cols);
         LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(d_dst, (size_t)dst_step, p0, (size_t)steps[0], 3 * (size_t)cols, (size_t)rows, hipMemcpyDeviceToDevice, stream));
         return LVK_HIP_OK;
     case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX:
-        // DirectIngest::to_ocl as written (FrameIngest.cpp:743-747): rows * cols * 3 BYTES of the tightly packed 4-byte pixels, viewed as 3-byte pixels
-        LVK_HIP_REQUIRE(ctx, steps[0] == 4 * cols && dst_step >= 3 * cols);
+        // (DirectIngest::to_ocl: the first rows * cols * 3 bytes of the tight 4-byte pixels, lvk_ingest_obs_check)
         LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(d_dst, (size_t)dst_step, p0, 3 * (size_t)cols, 3 * (size_t)cols, (size_t)rows, hipMemcpyDeviceToDevice, stream));
         return LVK_HIP_OK;
     default:

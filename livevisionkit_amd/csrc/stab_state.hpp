@@ -356,6 +356,7 @@ struct lvk_hip_stab
     bool is_retired(const void* p) const { for (void* q : pool_retired) if (q == p) return true; return false; }
     int release_retired(const void* p);        // frees a retired slot once nothing in flight reads it
     int sweep_retired();                       // retired slots whose frame left the queue outside a push (restart, a shrinking queue)
+    int return_slot(void* p, bool front = false);      // a slot back into pool_free: refused unless it is in pool_all and not free already
     int ensure_pool(int rows, int cols);
     void free_pool();
 };

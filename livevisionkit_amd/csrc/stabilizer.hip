@@ -624,12 +624,26 @@ int lvk_hip_stab::sweep_retired()
 {
     for (size_t i = 0; i < pool_retired.size();)
     {
-        bool queued = false;
+        // (the slot parked in pending_release -- DirectIngest's formats in overlap mode: its remap may still be running -- leaves through *released
+        //  at the next emit and is freed there; freeing it here handed the freed address back to pool_free one push later)
+        bool queued = pool_retired[i] == pending_release;
         for (const QueuedFrame& q : queue) queued = queued || q.d_ptr == pool_retired[i];
         if (queued) { i++; continue; }
         const int rc = release_retired(pool_retired[i]);
         if (rc != LVK_HIP_OK) return rc;
     }
+    return LVK_HIP_OK;
+}
+
+int lvk_hip_stab::return_slot(void* p, bool front)
+{
+    // a slot that comes back must be one of the current pool's and not free already: anything else is a freed (retired) address or a double
+    // return, which the next ingest would write into -- refused here, before anything reads or writes it
+    if (std::find(pool_all.begin(), pool_all.end(), p) == pool_all.end())
+        return fail(LVK_HIP_ERR_RUNTIME, "pool bookkeeping: a frame slot that is not in the current pool came back for reuse");
+    if (std::find(pool_free.begin(), pool_free.end(), p) != pool_free.end())
+        return fail(LVK_HIP_ERR_RUNTIME, "pool bookkeeping: a frame slot came back for reuse twice");
+    if (front) pool_free.push_front(p); else pool_free.push_back(p);
     return LVK_HIP_OK;
 }
 
@@ -677,6 +691,15 @@ int lvk_hip_stab_push(lvk_hip_stab* st, const void* d_frame, int step, int rows,
     return rc;
 }
 
+static const char* lvk_frame_format_name(int f)
+{
+    switch (f)
+    {
+    case LVK_FORMAT_BGR: return "BGR"; case LVK_FORMAT_BGRA: return "BGRA"; case LVK_FORMAT_RGB: return "RGB"; case LVK_FORMAT_RGBA: return "RGBA";
+    case LVK_FORMAT_YUV: return "YUV"; case LVK_FORMAT_GRAY: return "GRAY"; default: return "?";
+    }
+}
+
 // The OBS asynchronous path in one call: I4XXIngest / NV12Ingest::to_ocl -> StabilizationFilter::filter -> ::to_obs
 // (Modules/OBS-Plugin/Interop/VisionFilter.cpp:151-212, FrameIngest.cpp:494-602).  Planar (or NV12) 4:2:0 in, 4:2:0 out;
 // the packed 8UC3 frames the filter works on live in an internal pool (predictive_samples + 4 frames).  The input planes
@@ -695,6 +718,9 @@ static int lvk_stab_push_planes(lvk_hip_stab* st, int vf, const void* const in_p
     const int frame_format = lvk_hip_obs_frame_format(vf);
     if (frame_format < 0 || frame_format == LVK_FORMAT_GRAY || !in_planes || !in_steps || !in_planes[0])
         return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs: video format " + std::to_string(vf) + " has no three-channel frame the filter could take (FrameIngest::Select, lvk::remap: CV_8UC3)");
+    // what the conversion will read (planes, pitches, the parity of the size) is checked HERE, before the pool, the tracker or the queue changes: in overlap
+    // mode the conversion itself is launched only after track() and the queue have moved, and a refusal there left an unconverted slot queued
+    { const int rc0 = lvk_ingest_obs_check(ctx, vf, in_planes, in_steps, rows, cols); if (rc0 != LVK_HIP_OK) return rc0; }
     const std::array<const void*, 3> ip{in_planes[0], in_planes[1], in_planes[2]};
     const std::array<int, 3> is_{in_steps[0], in_steps[1], in_steps[2]};
     std::array<void*, 3> op{nullptr, nullptr, nullptr}; std::array<int, 3> os{0, 0, 0};
@@ -716,22 +742,27 @@ static int lvk_stab_push_planes(lvk_hip_stab* st, int vf, const void* const in_p
     if (produced) *produced = 0;
     if (st->queue.empty()) st->queue_kind = 0;
     if (st->queue_kind == 1) return st->fail(LVK_HIP_ERR_ARG, "borrowed frames of lvk_hip_stab_push are still queued: restart() before switching to lvk_hip_stab_push_yuv420");
-    if (!is420)
+    QueuedFrame due{};
+    const bool will_emit = st->next_output(QueuedFrame{nullptr, 3 * cols, rows, cols, timestamp, frame_format}, &due);
+    // The emitted frame leaves in THIS push's video format.  A delayed frame of the other format class (BGR / RGB against YUV) would be run through the
+    // wrong EASU program and written as the wrong bytes: the reference converts it into its own OBS frame (OBSFrame::to_obs_frame, viewAsFormat), which a
+    // one-format-per-push call cannot do -- refused, before anything changes (declared deviation, include/lvk_hip.h; restart() recovers).
+    if (will_emit && due.format != frame_format)
+        return st->fail(LVK_HIP_ERR_ARG, std::string("the frame this push emits was queued as ") + lvk_frame_format_name(due.format) + " and this push's planes are " +
+                                             lvk_frame_format_name(frame_format) + " (video format " + std::to_string(vf) + "): the emitted frame is not converted between BGR / RGB and YUV -- "
+                                             "restart() before switching; nothing was queued");
+    if (!is420 && will_emit)
     {
         // the planes of the frame this push emits (the DELAYED one, at its own size) must hold it: refused before anything changes, like the 4:2:0 planes
-        QueuedFrame due{};
-        if (st->next_output(QueuedFrame{nullptr, 3 * cols, rows, cols, timestamp, frame_format}, &due))
-        {
-            const int packed = (vf == LVK_VIDEO_FORMAT_YUY2 || vf == LVK_VIDEO_FORMAT_YVYU || vf == LVK_VIDEO_FORMAT_UYVY) ? 2 :
-                               (vf == LVK_VIDEO_FORMAT_AYUV || vf == LVK_VIDEO_FORMAT_RGBA || vf == LVK_VIDEO_FORMAT_BGRA || vf == LVK_VIDEO_FORMAT_BGRX) ? 4 :
-                               vf == LVK_VIDEO_FORMAT_BGR3 ? 3 : 0;
-            const int cw = (vf == LVK_VIDEO_FORMAT_I422 || vf == LVK_VIDEO_FORMAT_I42A) ? due.cols / 2 : due.cols;
-            const bool fits = op[0] && o_rows >= due.rows &&
-                              (packed ? os[0] >= packed * due.cols : (op[1] && op[2] && os[0] >= due.cols && os[1] >= cw && os[2] >= cw));
-            if (!fits)
-                return st->fail(LVK_HIP_ERR_ARG, "the output planes do not hold the frame this push emits: " + std::to_string(due.cols) + " x " + std::to_string(due.rows) +
-                                                     " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
-        }
+        const int packed = (vf == LVK_VIDEO_FORMAT_YUY2 || vf == LVK_VIDEO_FORMAT_YVYU || vf == LVK_VIDEO_FORMAT_UYVY) ? 2 :
+                           (vf == LVK_VIDEO_FORMAT_AYUV || vf == LVK_VIDEO_FORMAT_RGBA || vf == LVK_VIDEO_FORMAT_BGRA || vf == LVK_VIDEO_FORMAT_BGRX) ? 4 :
+                           vf == LVK_VIDEO_FORMAT_BGR3 ? 3 : 0;
+        const int cw = (vf == LVK_VIDEO_FORMAT_I422 || vf == LVK_VIDEO_FORMAT_I42A) ? due.cols / 2 : due.cols;
+        const bool fits = op[0] && o_rows >= due.rows &&
+                          (packed ? os[0] >= packed * due.cols : (op[1] && op[2] && os[0] >= due.cols && os[1] >= cw && os[2] >= cw));
+        if (!fits)
+            return st->fail(LVK_HIP_ERR_ARG, "the output planes do not hold the frame this push emits: " + std::to_string(due.cols) + " x " + std::to_string(due.rows) +
+                                                 " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
     }
     st->queue_kind = 2;
     int rc = st->ensure_pool(rows, cols);
@@ -785,7 +816,7 @@ static int lvk_stab_push_planes(lvk_hip_stab* st, int vf, const void* const in_p
     // launch and its event record wait until the tracker's kernels are on their way -- track() calls it after its last launch.
     // (8.05k -> 8.17k frames/s, p50 latency -7 us.)
     if (side_ingest) st->deferred_ingest = do_ingest;
-    else { rc = do_ingest(); if (rc != LVK_HIP_OK) { st->pool_free.push_back(slot); return rc; } }
+    else { rc = do_ingest(); if (rc != LVK_HIP_OK) { const int r1 = st->return_slot(slot); return r1 != LVK_HIP_OK ? r1 : rc; } }
     int prod = 0; const void* released = nullptr;
     st->pool_frames = side_ingest;
     OutPlanes420 o420{o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, false, o_rows};
@@ -806,13 +837,13 @@ static int lvk_stab_push_planes(lvk_hip_stab* st, int vf, const void* const in_p
         // a push that was refused (or failed before the frame was queued) has not taken the slot: its conversion is not launched, the slot is free again
         bool taken = released == slot;
         for (const QueuedFrame& q : st->queue) taken = taken || q.d_ptr == slot;
-        if (!taken) { st->deferred_ingest = nullptr; st->pool_free.push_front(slot); }
+        if (!taken) { st->deferred_ingest = nullptr; const int r1 = st->return_slot(slot, true); if (rc == LVK_HIP_OK) rc = r1; }
     }
     if (st->deferred_ingest) { const int r2 = st->run_deferred_ingest(); if (rc == LVK_HIP_OK) rc = r2; }      // (track() returned before its launches)
     if (released)
     {
         if (st->is_retired(released)) { const int r3 = st->release_retired(released); if (rc == LVK_HIP_OK) rc = r3; }      // a frame of an earlier size has left
-        else st->pool_free.push_back(const_cast<void*>(released));
+        else { const int r3 = st->return_slot(const_cast<void*>(released)); if (rc == LVK_HIP_OK) rc = r3; }
     }
     if (emitted && prod) *emitted = info;
     if (side_ingest)
