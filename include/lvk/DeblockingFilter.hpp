@@ -1,0 +1,102 @@
+// lvk::DeblockingFilter of the C++ facade (Filters/DeblockingFilter.{hpp,cpp}) over lvk_hip_deblock_* of lvk_hip.h: same names, settings
+// and defaults.  apply(frame, frame) deblocks in place, as the OBS plugin's ADB filter calls it (Modules/OBS-Plugin/Sources/Enhancement/
+// ADBFilter.cpp:130-136: apply(frame, frame, true), then draw_influence(frame) in test mode); the filter chains in CompositeFilter and takes the
+// frames FrameIngest::upload_obs_frame makes.  Included by LiveVisionKit.hpp.
+#pragma once
+
+#include "LiveVisionKit.hpp"
+
+namespace lvk {
+
+struct DeblockingFilterSettings                      // Filters/DeblockingFilter.hpp:27-33
+{
+    uint32_t detection_levels = 3;   // Must be greater than 0
+    uint32_t block_size = 16;        // Must be greater than 0
+    uint32_t filter_size = 5;        // Must be odd
+    float filter_scaling = 4;        // Smaller is stronger (1/x)
+};
+
+class DeblockingFilter final : public VideoFilter, public Configurable<DeblockingFilterSettings>
+{
+public:
+    explicit DeblockingFilter(const DeblockingFilterSettings& settings = {}) : VideoFilter("Deblocking Filter") { configure(settings); }
+    ~DeblockingFilter() override
+    {
+        if (!m_Handle) return;
+        hip::ContextLock lock(m_Ctx->mutex());
+        lvk_hip_deblock_destroy(m_Handle);
+    }
+    DeblockingFilter(const DeblockingFilter&) = delete;
+    DeblockingFilter& operator=(const DeblockingFilter&) = delete;
+
+    void configure(const DeblockingFilterSettings& settings) override           // DeblockingFilter.cpp:35-45
+    {
+        LVK_HIP_ASSERT(settings.block_size > 0);
+        LVK_HIP_ASSERT(settings.filter_size >= 3);
+        LVK_HIP_ASSERT(settings.filter_size % 2 == 1);
+        LVK_HIP_ASSERT(settings.detection_levels > 0);
+        LVK_HIP_ASSERT(settings.filter_scaling > 1.0f);
+        m_Settings = settings;
+        if (m_Handle)
+        {
+            const lvk_deblock_settings s = to_c(settings);
+            hip::ContextLock lock(m_Ctx->mutex());
+            m_Ctx->check(lvk_hip_deblock_configure(m_Handle, &s), "DeblockingFilter::configure");
+        }
+    }
+
+    void draw_influence(VideoFrame& frame) const                                  // DeblockingFilter.cpp:114-131
+    {
+        LVK_HIP_ASSERT(m_Handle != nullptr && !frame.empty());
+        hip::ContextLock lock(m_Ctx->mutex());
+        fence_in(frame);
+        m_Ctx->check(lvk_hip_deblock_draw_influence(m_Handle, frame.device_ptr(), (int)frame.step, frame.rows, frame.cols, (int)frame.format),
+                     "DeblockingFilter::draw_influence");
+        fence_out(frame);
+    }
+
+    cv::Rect filter_region() const                                                // DeblockingFilter.cpp:135-138
+    {
+        int r[4] = {0, 0, 0, 0};
+        if (m_Handle) lvk_hip_deblock_filter_region(m_Handle, r);
+        return cv::Rect(r[0], r[1], r[2], r[3]);
+    }
+
+private:
+    static lvk_deblock_settings to_c(const DeblockingFilterSettings& s)
+    {
+        lvk_deblock_settings c;
+        c.detection_levels = s.detection_levels; c.block_size = s.block_size; c.filter_size = s.filter_size; c.filter_scaling = s.filter_scaling;
+        return c;
+    }
+    // frames of another context (a chain whose stages run on different streams) are fenced in both directions around the filter's work
+    void fence_in(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) m_Ctx->wait_for(*frame.context()); }
+    void fence_out(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) frame.context()->wait_for(*m_Ctx); }
+
+    void filter(VideoFrame&& input, VideoFrame& output) override                  // DeblockingFilter.cpp:48-110, in place
+    {
+        LVK_HIP_ASSERT(!input.empty());
+        VideoFrame frame = std::move(input);
+        if (!m_Handle)
+        {
+            m_Ctx = frame.context();
+            const lvk_deblock_settings s = to_c(m_Settings);
+            hip::ContextLock lock(m_Ctx->mutex());
+            m_Ctx->check(lvk_hip_deblock_create(m_Ctx->get(), &s, &m_Handle), "DeblockingFilter");
+        }
+        {
+            hip::ContextLock lock(m_Ctx->mutex());
+            fence_in(frame);
+            m_Ctx->check(lvk_hip_deblock_apply(m_Handle, frame.device_ptr(), (int)frame.step, frame.rows, frame.cols, (int)frame.format, nullptr),
+                         "DeblockingFilter::filter");
+            fence_out(frame);
+        }
+        output = std::move(frame);
+    }
+    void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
+
+    std::shared_ptr<hip::Context> m_Ctx;
+    lvk_hip_deblock* m_Handle = nullptr;
+};
+
+} // namespace lvk

@@ -965,3 +965,6 @@ using GridDetectorSettings = FeatureDetectorSettings;
 
 // Math/Homography.hpp, Math/WarpMesh.hpp, the lvk::remap launchers of Functions/Image.hpp
 #include "WarpMesh.hpp"
+
+// Filters/DeblockingFilter.hpp
+#include "DeblockingFilter.hpp"

@@ -61,7 +61,7 @@ const char* lvk_hip_last_error(lvk_hip_ctx* ctx);    /* NULL ctx: last error of 
 const char* lvk_hip_version(void);                   /* human-readable build string */
 /* ABI number of PART 1 of this header as the library was built (compare with LVK_HIP_ABI_VERSION of the header a host was compiled against;
  * tests/test_abi.py holds the two together). */
-#define LVK_HIP_ABI_VERSION 6
+#define LVK_HIP_ABI_VERSION 7
 int  lvk_hip_abi_version(void);
 /* Devices of this process: contexts are addressed by HIP device index, and lvk_hip_device_count() is the number of indices worth trying -- the
  * highest gfx950 index + 1 (0 when there is no gfx950 device; never an error).  On the usual host every index below it is an MI355X; on a mixed
@@ -366,6 +366,37 @@ int  lvk_hip_stab_set_bulk_context(lvk_hip_stab* stab, lvk_hip_ctx* bulk);
 void* lvk_hip_stab_output_stream(lvk_hip_stab* stab);
 
 
+/* ---- the deblocking filter ----------------------------------------------------------------------------------------------------------
+ * lvk::DeblockingFilter (Filters/DeblockingFilter.{hpp,cpp}; the OBS plugin's "ADB" filter and the editor's `adb` stage): blends a median-
+ * smoothed copy of the frame into it where its macroblocks are flat.  lvk_deblock_settings = DeblockingFilterSettings (DeblockingFilter.hpp:
+ * 27-33), same names and defaults (lvk_hip_deblock_default_settings: 3, 16, 5, 4.0f).  create / configure refuse (LVK_HIP_ERR_ARG, nothing
+ * changes) a settings struct unless block_size > 0, filter_size >= 3 and odd, detection_levels > 0 and filter_scaling > 1 (:35-45). */
+typedef struct lvk_deblock_settings
+{
+    uint32_t detection_levels;     /* 3 */
+    uint32_t block_size;           /* 16 */
+    uint32_t filter_size;          /* 5 */
+    float filter_scaling;          /* 4.0f */
+} lvk_deblock_settings;
+
+typedef struct lvk_hip_deblock lvk_hip_deblock;
+
+void lvk_hip_deblock_default_settings(lvk_deblock_settings* s);
+int  lvk_hip_deblock_create(lvk_hip_ctx* ctx, const lvk_deblock_settings* settings, lvk_hip_deblock** out);   /* settings NULL: defaults */
+int  lvk_hip_deblock_configure(lvk_hip_deblock* deb, const lvk_deblock_settings* settings);                    /* :35-45 */
+void lvk_hip_deblock_destroy(lvk_hip_deblock* deb);
+/* VideoFilter::apply(frame, frame) -> DeblockingFilter::filter (:48-110), IN PLACE on a packed 8UC3 device frame of any pitch (step >= 3 * cols)
+ * of format LVK_FORMAT_BGR, _RGB or _YUV.  Only the region of whole block_size x block_size macroblocks at the top left is written; *region_xywh
+ * (optional) = that region.  Refused with LVK_HIP_ERR_ARG before anything changes (frame and filter as they were): GRAY and 4-channel formats,
+ * a frame without one whole macroblock or whose 1 / filter_scaling downscale is empty (the reference throws from cv::resize), filter_size > 255.
+ * Asynchronous on the context's stream; the first call at a new geometry builds its interpolation tables. */
+int  lvk_hip_deblock_apply(lvk_hip_deblock* deb, void* d_frame, int step, int rows, int cols, int format, int region_xywh[4]);
+/* DeblockingFilter::draw_influence (:114-131): blends MAGENTA[format] into the region of the last apply with that apply's blend maps.  Refused
+ * before the first apply and when that region does not fit the frame. */
+int  lvk_hip_deblock_draw_influence(const lvk_hip_deblock* deb, void* d_frame, int step, int rows, int cols, int format);
+int  lvk_hip_deblock_filter_region(const lvk_hip_deblock* deb, int region_xywh[4]);       /* :135-138; (0, 0, 0, 0) before the first apply */
+
+
 /* =====================================================================================================================================
  * PART 2 -- EXPERIMENTAL / DIAGNOSTICS  (no ABI promise: per-stage entry points of the parity tests, taps, profiling, device look-ahead)
  * ===================================================================================================================================== */
@@ -503,6 +534,11 @@ int lvk_hip_estimate_global_motion(lvk_hip_ctx* ctx, const float* pts1, const fl
  * flow and the motion estimate: keeps the pairs whose status is non-zero, in the order the reference's back-to-front swap-erase
  * leaves them.  Host arrays (n x 2 floats, n bytes); returns the number of pairs kept (>= 0) or LVK_HIP_ERR_*. */
 int lvk_hip_fast_filter(lvk_hip_ctx* ctx, const float* prev, const float* matched, const uint8_t* status, int n, float* out_prev, float* out_matched);
+
+/* Deblocking tap: the block grids of the last apply (synchronises the context's stream).  mean = the 8U block means, grid = the 8U mean absolute
+ * deviations from them, keep_block = float(min(grid, L) * (1.0 / L)); ex * ey values each, row-major (NULL: skipped).  extent_xy = (ex, ey).
+ * Returns ex * ey, or LVK_HIP_ERR_ARG before the first apply or when capacity < ex * ey. */
+int lvk_hip_deblock_get_grid(lvk_hip_deblock* deb, uint8_t* mean, uint8_t* grid, float* keep_block, int capacity, int extent_xy[2]);
 
 #ifdef __cplusplus
 }

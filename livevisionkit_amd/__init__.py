@@ -7,6 +7,7 @@ bench driver: it calls the C-ABI through ctypes and uses torch only for device m
 from . import _native
 from .context import Context, LvkHipError
 from .stabilization import StabilizationFilter, StabilizationFilterSettings
+from .deblocking import DeblockingFilter, DeblockingFilterSettings
 from . import shard
 
-__all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "_native"]
+__all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "_native"]

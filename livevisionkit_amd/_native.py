@@ -110,6 +110,14 @@ _SIG = {
     "lvk_hip_stab_set_bulk_context": (_c.c_int, [_P, _P]),
     "lvk_hip_stab_set_profiling": (_c.c_int, [_P, _c.c_int]),
     "lvk_hip_stab_get_profile": (_c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_longlong)]),
+    "lvk_hip_deblock_default_settings": (None, [_P]),
+    "lvk_hip_deblock_create": (_c.c_int, [_P, _P, _c.POINTER(_P)]),
+    "lvk_hip_deblock_configure": (_c.c_int, [_P, _P]),
+    "lvk_hip_deblock_destroy": (None, [_P]),
+    "lvk_hip_deblock_apply": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+    "lvk_hip_deblock_draw_influence": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_deblock_filter_region": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),
+    "lvk_hip_deblock_get_grid": (_c.c_int, [_P, _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_float), _c.c_int, _c.POINTER(_c.c_int)]),
 }
 
 _lib = None

@@ -1,0 +1,91 @@
+"""Host-side mirror of lvk::DeblockingFilter (reference: LiveVisionKit/Filters/DeblockingFilter.hpp:26-57) over the C-ABI.
+Same method names: configure / apply / draw_influence / filter_region.  Frames are torch uint8 tensors [rows, cols, 3] on the GPU
+(any row pitch: a view with stride(1) == 3 and stride(2) == 1), filtered IN PLACE like the reference's apply(frame, frame)."""
+import ctypes
+
+import numpy as np
+
+from . import _native
+from .stabilization import FORMAT_YUV
+
+_c = ctypes
+
+
+class DeblockingFilterSettings(_c.Structure):
+    """lvk::DeblockingFilterSettings (field-for-field lvk_deblock_settings of include/lvk_hip.h)."""
+    _fields_ = [("detection_levels", _c.c_uint32), ("block_size", _c.c_uint32), ("filter_size", _c.c_uint32), ("filter_scaling", _c.c_float)]
+
+    def __init__(self, **over):
+        super().__init__()
+        _native.load().lvk_hip_deblock_default_settings(_c.byref(self))
+        for k, v in over.items():
+            setattr(self, k, v)
+
+
+def _frame_args(frame):
+    if frame.dim() != 3 or frame.shape[2] != 3 or frame.stride(2) != 1 or frame.stride(1) != 3 or frame.dtype.itemsize != 1:
+        raise ValueError("a packed 8UC3 frame [rows, cols, 3] with contiguous rows is required")
+    return frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1]
+
+
+class DeblockingFilter:
+    """DeblockingFilter(ctx, **settings): settings by name (detection_levels, block_size, filter_size, filter_scaling) or settings=..."""
+
+    def __init__(self, ctx, settings=None, **over):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        s = settings if settings is not None else DeblockingFilterSettings(**over)
+        handle = _c.c_void_p()
+        ctx._check(self.lib.lvk_hip_deblock_create(ctx.handle, _c.byref(s), _c.byref(handle)))
+        self.handle = handle
+        self.settings = s
+
+    def configure(self, settings=None, **over):
+        s = settings if settings is not None else DeblockingFilterSettings(**over)
+        self.ctx._check(self.lib.lvk_hip_deblock_configure(self.handle, _c.byref(s)))
+        self.settings = s
+
+    def apply(self, frame, fmt=FORMAT_YUV):
+        """Deblocks `frame` in place (asynchronous on the context's stream); returns the filter region (x, y, w, h)."""
+        region = (_c.c_int * 4)()
+        self.ctx._check(self.lib.lvk_hip_deblock_apply(self.handle, *_frame_args(frame), int(fmt), region))
+        return tuple(region)
+
+    def draw_influence(self, frame, fmt=FORMAT_YUV):
+        self.ctx._check(self.lib.lvk_hip_deblock_draw_influence(self.handle, *_frame_args(frame), int(fmt)))
+
+    def filter_region(self):
+        region = (_c.c_int * 4)()
+        self.ctx._check(self.lib.lvk_hip_deblock_filter_region(self.handle, region))
+        return tuple(region)
+
+    def grid(self):
+        """Diagnostics tap: (mean, grid, keep_block) of the last apply as [ey, ex] numpy arrays (synchronises the stream)."""
+        ext = (_c.c_int * 2)()
+        x, y, w, h = self.filter_region()
+        bs = int(self.settings.block_size) or 1
+        cap = max(1, (w // bs) * (h // bs))
+        while True:
+            mean = np.zeros(cap, np.uint8); grid = np.zeros(cap, np.uint8); keep = np.zeros(cap, np.float32)
+            n = self.lib.lvk_hip_deblock_get_grid(self.handle, mean.ctypes.data_as(_c.POINTER(_c.c_uint8)), grid.ctypes.data_as(_c.POINTER(_c.c_uint8)),
+                                                  keep.ctypes.data_as(_c.POINTER(_c.c_float)), cap, ext)
+            if n >= 0 or ext[0] * ext[1] <= cap:
+                break
+            cap = ext[0] * ext[1]          # configured to another block size since the last apply
+        self.ctx._check(min(n, 0))
+        shape = (ext[1], ext[0])
+        return mean[:n].reshape(shape), grid[:n].reshape(shape), keep[:n].reshape(shape)
+
+    def close(self):
+        # (a filter that outlives its context -- a failed test whose traceback keeps it alive past the session's Context -- must not hand a
+        #  dangling context to the library: the handle is dropped, its buffers went with the context's pool)
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):
+                self.lib.lvk_hip_deblock_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
