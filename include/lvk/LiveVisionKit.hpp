@@ -968,3 +968,6 @@ using GridDetectorSettings = FeatureDetectorSettings;
 
 // Filters/DeblockingFilter.hpp
 #include "DeblockingFilter.hpp"
+
+// the OBS plugin's CAS filter (Sources/Enhancement/CASFilter.cpp, Effects/CASEffect.cpp)
+#include "CASFilter.hpp"

@@ -61,7 +61,7 @@ const char* lvk_hip_last_error(lvk_hip_ctx* ctx);    /* NULL ctx: last error of 
 const char* lvk_hip_version(void);                   /* human-readable build string */
 /* ABI number of PART 1 of this header as the library was built (compare with LVK_HIP_ABI_VERSION of the header a host was compiled against;
  * tests/test_abi.py holds the two together). */
-#define LVK_HIP_ABI_VERSION 7
+#define LVK_HIP_ABI_VERSION 8
 int  lvk_hip_abi_version(void);
 /* Devices of this process: contexts are addressed by HIP device index, and lvk_hip_device_count() is the number of indices worth trying -- the
  * highest gfx950 index + 1 (0 when there is no gfx950 device; never an error).  On the usual host every index below it is an MI355X; on a mixed
@@ -396,6 +396,16 @@ int  lvk_hip_deblock_apply(lvk_hip_deblock* deb, void* d_frame, int step, int ro
 int  lvk_hip_deblock_draw_influence(const lvk_hip_deblock* deb, void* d_frame, int step, int rows, int cols, int format);
 int  lvk_hip_deblock_filter_region(const lvk_hip_deblock* deb, int region_xywh[4]);       /* :135-138; (0, 0, 0, 0) before the first apply */
 
+/* ---- contrast adaptive sharpening ---------------------------------------------------------------------------------------------------
+ * The OBS plugin's CAS filter (Sources/Enhancement/CASFilter.cpp, Effects/CASEffect.cpp, the FidelityFX CasFilter of cas.effect with CAS_SLOW
+ * and CAS_BETTER_DIAGONALS): d_dst = CAS(d_src), OUT OF PLACE, on a packed frame of format LVK_FORMAT_BGR, _RGB or _YUV (3 channels) or
+ * LVK_FORMAT_BGRA, _RGBA (4 channels; the 4th byte is written as 255, the shader's float4(col, 1.0)).  Every channel is sharpened on its own,
+ * the neighbours outside the frame read as 0, and only the cols * channels bytes of each destination row are written (any pitch, any byte
+ * alignment).  sharpness in [0, 1] (the filter's default is 0.8).  Refused with LVK_HIP_ERR_ARG, the destination untouched: GRAY or
+ * unknown formats, sharpness outside [0, 1] or NaN, rows or cols <= 0, a step < cols * channels, a NULL pointer, and source and destination
+ * byte ranges that overlap (in place would race: CAS reads its neighbours).  Asynchronous on the context's stream. */
+int  lvk_hip_cas(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, int format, void* d_dst, int dst_step, float sharpness);
+
 
 /* =====================================================================================================================================
  * PART 2 -- EXPERIMENTAL / DIAGNOSTICS  (no ABI promise: per-stage entry points of the parity tests, taps, profiling, device look-ahead)
@@ -539,6 +549,10 @@ int lvk_hip_fast_filter(lvk_hip_ctx* ctx, const float* prev, const float* matche
  * deviations from them, keep_block = float(min(grid, L) * (1.0 / L)); ex * ey values each, row-major (NULL: skipped).  extent_xy = (ex, ey).
  * Returns ex * ey, or LVK_HIP_ERR_ARG before the first apply or when capacity < ex * ey. */
 int lvk_hip_deblock_get_grid(lvk_hip_deblock* deb, uint8_t* mean, uint8_t* grid, float* keep_block, int capacity, int extent_xy[2]);
+
+/* CAS host constant (CasSetup's const1.x, float32, each operation rounded on its own): peak = -(1 / (5 s + ((-8) s + 8))) with
+ * s = clamp(sharpness, 0, 1).  Needs no device.  LVK_HIP_ERR_ARG for a NaN sharpness or a NULL peak. */
+int lvk_hip_cas_const(float sharpness, float* peak);
 
 #ifdef __cplusplus
 }

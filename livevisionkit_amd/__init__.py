@@ -8,6 +8,8 @@ from . import _native
 from .context import Context, LvkHipError
 from .stabilization import StabilizationFilter, StabilizationFilterSettings
 from .deblocking import DeblockingFilter, DeblockingFilterSettings
+from .cas import CASFilter
 from . import shard
 
-__all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "_native"]
+__all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "CASFilter",
+           "_native"]

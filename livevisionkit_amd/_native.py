@@ -118,6 +118,8 @@ _SIG = {
     "lvk_hip_deblock_draw_influence": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_deblock_filter_region": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),
     "lvk_hip_deblock_get_grid": (_c.c_int, [_P, _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_float), _c.c_int, _c.POINTER(_c.c_int)]),
+    "lvk_hip_cas": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
+    "lvk_hip_cas_const": (_c.c_int, [_c.c_float, _c.POINTER(_c.c_float)]),
 }
 
 _lib = None
