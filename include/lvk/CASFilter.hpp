@@ -1,7 +1,7 @@
 // lvk::CASFilter of the C++ facade: the OBS plugin's CAS filter (Modules/OBS-Plugin/Sources/Enhancement/CASFilter.cpp, Effects/CASEffect.cpp:
 // contrast adaptive sharpening, FidelityFX CasFilter with CAS_SLOW and CAS_BETTER_DIAGONALS) over lvk_hip_cas of lvk_hip.h.  The plugin runs
 // it as an OBS graphics effect; here it is a VideoFilter, so it chains in CompositeFilter (deblock, then sharpen) and takes the frames
-// FrameIngest::upload_obs_frame makes.  The facade's frames are 8UC3: BGR / RGB / YUV.  The 4-channel formats are reached through the C-ABI.
+// FrameIngest::upload_obs_frame makes: BGR / RGB / YUV, and BGRA / RGBA frames of 4 channels (VideoFrame::reformat, ConversionFilter).
 // Included by LiveVisionKit.hpp.
 #pragma once
 
@@ -38,7 +38,7 @@ private:
         VideoFrame src = std::move(input);          // CAS reads its neighbours: out of place, into a fresh frame
         if (!m_Ctx) m_Ctx = src.context();
         VideoFrame dst(src.timestamp);
-        dst.create(src.size(), CV_8UC3, m_Ctx);
+        dst.create(src.size(), src.type(), m_Ctx);
         dst.format = src.format;
         {
             hip::ContextLock lock(m_Ctx->mutex());

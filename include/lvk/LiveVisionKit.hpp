@@ -109,29 +109,34 @@ struct VideoFrame
 
     VideoFrame() = default;
     explicit VideoFrame(uint64_t ts) : timestamp(ts) {}
-    VideoFrame(const VideoFrame& o) : timestamp(o.timestamp), format(o.format), cols(o.cols), rows(o.rows), step(o.step), m_buf(o.m_buf), m_ctx(o.m_ctx) {}
-    VideoFrame(VideoFrame&& o) noexcept : timestamp(o.timestamp), format(o.format), cols(o.cols), rows(o.rows), step(o.step), m_buf(std::move(o.m_buf)), m_ctx(std::move(o.m_ctx)) { o.cols = o.rows = 0; o.step = 0; }
-    VideoFrame& operator=(const VideoFrame& o) { timestamp = o.timestamp; format = o.format; cols = o.cols; rows = o.rows; step = o.step; m_buf = o.m_buf; m_ctx = o.m_ctx; return *this; }
+    VideoFrame(const VideoFrame& o) : timestamp(o.timestamp), format(o.format), cols(o.cols), rows(o.rows), step(o.step), m_buf(o.m_buf), m_ctx(o.m_ctx), m_channels(o.m_channels) {}
+    VideoFrame(VideoFrame&& o) noexcept : timestamp(o.timestamp), format(o.format), cols(o.cols), rows(o.rows), step(o.step), m_buf(std::move(o.m_buf)), m_ctx(std::move(o.m_ctx)), m_channels(o.m_channels) { o.cols = o.rows = 0; o.step = 0; }
+    VideoFrame& operator=(const VideoFrame& o) { timestamp = o.timestamp; format = o.format; cols = o.cols; rows = o.rows; step = o.step; m_buf = o.m_buf; m_ctx = o.m_ctx; m_channels = o.m_channels; return *this; }
     VideoFrame& operator=(VideoFrame&& o) noexcept
     {
         timestamp = o.timestamp; format = o.format; cols = o.cols; rows = o.rows; step = o.step; m_buf = std::move(o.m_buf); m_ctx = std::move(o.m_ctx);
-        o.cols = o.rows = 0; o.step = 0; return *this;
+        m_channels = o.m_channels; o.cols = o.rows = 0; o.step = 0; return *this;
     }
     virtual ~VideoFrame() = default;
 
     // cv::UMat subset
     bool empty() const { return !m_buf || cols == 0 || rows == 0; }
     cv::Size size() const { return {cols, rows}; }
-    int type() const { return CV_8UC3; }
+    int type() const { return m_channels == 1 ? CV_8UC1 : m_channels == 4 ? CV_8UC4 : CV_8UC3; }
+    int channels() const { return m_channels; }
     void release() { m_buf.reset(); cols = rows = 0; step = 0; }
-    void create(const cv::Size& sz, int /*type = CV_8UC3*/, const std::shared_ptr<hip::Context>& ctx = nullptr)
+    // type: CV_8UC1, CV_8UC3 or CV_8UC4 (packed 8-bit, 1, 3 or 4 channels)
+    void create(const cv::Size& sz, int type, const std::shared_ptr<hip::Context>& ctx = nullptr)
     {
-        if (m_buf && m_buf.use_count() == 1 && cols == sz.width && rows == sz.height && (!ctx || ctx == m_ctx)) return;
+        LVK_HIP_ASSERT(type == CV_8UC1 || type == CV_8UC3 || type == CV_8UC4);
+        const int ch = type == CV_8UC1 ? 1 : type == CV_8UC4 ? 4 : 3;
+        if (m_buf && m_buf.use_count() == 1 && cols == sz.width && rows == sz.height && m_channels == ch && (!ctx || ctx == m_ctx)) return;
         // lvk_hip_malloc / lvk_hip_free pool by size (like cv::UMat's OpenCL buffer pool): no hipMalloc / hipFree in steady state.
         // A frame's buffer is written on its context's stream; a filter that reads it on another stream fences it back before dropping it.
         m_ctx = ctx ? ctx : (m_ctx ? m_ctx : hip::shared_context());
         void* p = nullptr;
-        step = (size_t)sz.width * 3;
+        m_channels = ch;
+        step = (size_t)sz.width * ch;
         m_ctx->check(lvk_hip_malloc(m_ctx->get(), step * (size_t)sz.height, &p), "VideoFrame::create");
         auto c = m_ctx;
         m_buf = std::shared_ptr<void>(p, [c](void* q) { lvk_hip_free(c->get(), q); });
@@ -140,10 +145,14 @@ struct VideoFrame
     void* device_ptr() const { return m_buf.get(); }
     bool has_known_format() const { return format != UNKNOWN; }
 
-    // host <-> device helpers (reference: cv::UMat::copyTo / getMat); packed 8UC3, tight rows
+    // the packed layout of a format: 1 channel for GRAY, 4 for BGRA / RGBA, 3 for BGR / RGB / YUV (and UNKNOWN)
+    static int channels_of(Format f) { return f == GRAY ? 1 : (f == BGRA || f == RGBA) ? 4 : 3; }
+    static int type_of(Format f) { return f == GRAY ? CV_8UC1 : (f == BGRA || f == RGBA) ? CV_8UC4 : CV_8UC3; }
+
+    // host <-> device helpers (reference: cv::UMat::copyTo / getMat); packed, tight rows of cols * channels_of(fmt) bytes
     void upload(const uint8_t* host, int rows_, int cols_, Format fmt, uint64_t ts, const std::shared_ptr<hip::Context>& ctx = nullptr)
     {
-        create({cols_, rows_}, CV_8UC3, ctx);
+        create({cols_, rows_}, type_of(fmt), ctx);
         hip::ContextLock lock(m_ctx->mutex());
         m_ctx->check(lvk_hip_upload(m_ctx->get(), m_buf.get(), host, step * (size_t)rows), "VideoFrame::upload");
         format = fmt; timestamp = ts;
@@ -160,16 +169,58 @@ struct VideoFrame
     {
         VideoFrame c;
         if (empty()) return c;
-        c.create(size(), CV_8UC3, m_ctx);
+        c.create(size(), type(), m_ctx);
         hip::ContextLock lock(m_ctx->mutex());
-        m_ctx->check(lvk_hip_upscale(m_ctx->get(), m_buf.get(), (int)step, rows, cols, c.m_buf.get(), (int)c.step, rows, cols, 1), "VideoFrame::clone");
+        if (m_channels == 3)
+            m_ctx->check(lvk_hip_upscale(m_ctx->get(), m_buf.get(), (int)step, rows, cols, c.m_buf.get(), (int)c.step, rows, cols, 1), "VideoFrame::clone");
+        else                                               // a 2-D copy (lvk_hip_reformat with the same format on both sides)
+        {
+            const int f = m_channels == 1 ? LVK_FORMAT_GRAY : LVK_FORMAT_BGRA;
+            m_ctx->check(lvk_hip_reformat(m_ctx->get(), m_buf.get(), (int)step, rows, cols, f, c.m_buf.get(), (int)c.step, f), "VideoFrame::clone");
+        }
         c.timestamp = timestamp; c.format = format;
         return c;
+    }
+
+    // VideoFrame::reformatTo (Data/VideoFrame.cpp:170-301): dst = this frame converted to new_format (OpenCV's 8-bit cvtColor; a copy when
+    // the format stays), asynchronous on this frame's context.  dst takes the timestamp and the format; it must not share this buffer.
+    void reformatTo(VideoFrame& dst, const Format new_format) const
+    {
+        LVK_HIP_ASSERT(new_format != UNKNOWN);
+        LVK_HIP_ASSERT(format != UNKNOWN);
+        LVK_HIP_ASSERT(!empty() && channels_of(format) == m_channels);
+        LVK_HIP_ASSERT(m_buf != dst.m_buf);
+        const std::shared_ptr<hip::Context> ctx = m_ctx;       // dst may be a frame of another context: the result lives on this one
+        dst.create(size(), type_of(new_format), ctx);
+        {
+            hip::ContextLock lock(ctx->mutex());
+            ctx->check(lvk_hip_reformat(ctx->get(), m_buf.get(), (int)step, rows, cols, (int)format, dst.m_buf.get(), (int)dst.step,
+                                        (int)new_format), "VideoFrame::reformatTo");
+        }
+        dst.timestamp = timestamp;
+        dst.format = new_format;
+    }
+    // VideoFrame::reformat (:155-168): converts in place; the converted pixels take a buffer of the context's pool, the old one returns to it
+    void reformat(const Format new_format)
+    {
+        LVK_HIP_ASSERT(new_format != UNKNOWN);
+        LVK_HIP_ASSERT(format != UNKNOWN);
+        if (new_format == format) return;
+        VideoFrame converted;
+        reformatTo(converted, new_format);
+        *this = std::move(converted);
+    }
+    // VideoFrame::viewAsFormat (:303-310): the same format shares this buffer, another is converted into view
+    void viewAsFormat(VideoFrame& view, const Format new_format) const
+    {
+        if (new_format != format) reformatTo(view, new_format);
+        else view = *this;
     }
 
 private:
     std::shared_ptr<void> m_buf;
     std::shared_ptr<hip::Context> m_ctx;
+    int m_channels = 3;
 };
 typedef VideoFrame Frame;
 
@@ -971,3 +1022,6 @@ using GridDetectorSettings = FeatureDetectorSettings;
 
 // the OBS plugin's CAS filter (Sources/Enhancement/CASFilter.cpp, Effects/CASEffect.cpp)
 #include "CASFilter.hpp"
+
+// Filters/ConversionFilter.hpp
+#include "ConversionFilter.hpp"

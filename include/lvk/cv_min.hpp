@@ -1,5 +1,6 @@
 // Minimal stand-ins for the handful of OpenCV value types that appear in the PUBLIC signatures of the
-// stabilization path (cv::Size, Size2f, Point, Point2f, Rect, Rect2f, Scalar).  Used only when the build has no
+// stabilization path (cv::Size, Size2f, Point, Point2f, Rect, Rect2f, Scalar), and the ColorConversionCodes
+// of ConversionFilter.  Used only when the build has no
 // OpenCV (this image has none); with -DLVK_WITH_OPENCV the real <opencv2/core.hpp> types are used instead.
 // Only what the reference's callers touch is provided (Modules/OBS-Plugin/Sources/Stabilisation/VSFilter.cpp:235-383).
 #pragma once
@@ -57,12 +58,31 @@ struct Scalar
     const double& operator[](int i) const { return val[i]; }
 };
 
-constexpr int CV_8UC1_ = 0, CV_8UC3_ = 16;
+constexpr int CV_8UC1_ = 0, CV_8UC3_ = 16, CV_8UC4_ = 24;
+
+// the cv::ColorConversionCodes that lvk::ConversionFilter takes (imgproc.hpp values)
+enum ColorConversionCodes
+{
+    COLOR_BGR2BGRA = 0, COLOR_RGB2RGBA = COLOR_BGR2BGRA,
+    COLOR_BGRA2BGR = 1, COLOR_RGBA2RGB = COLOR_BGRA2BGR,
+    COLOR_BGR2RGBA = 2, COLOR_RGB2BGRA = COLOR_BGR2RGBA,
+    COLOR_RGBA2BGR = 3, COLOR_BGRA2RGB = COLOR_RGBA2BGR,
+    COLOR_BGR2RGB = 4, COLOR_RGB2BGR = COLOR_BGR2RGB,
+    COLOR_BGRA2RGBA = 5, COLOR_RGBA2BGRA = COLOR_BGRA2RGBA,
+    COLOR_BGR2GRAY = 6, COLOR_RGB2GRAY = 7,
+    COLOR_GRAY2BGR = 8, COLOR_GRAY2RGB = COLOR_GRAY2BGR,
+    COLOR_GRAY2BGRA = 9, COLOR_GRAY2RGBA = COLOR_GRAY2BGRA,
+    COLOR_BGRA2GRAY = 10, COLOR_RGBA2GRAY = 11,
+    COLOR_BGR2YUV = 82, COLOR_RGB2YUV = 83, COLOR_YUV2BGR = 84, COLOR_YUV2RGB = 85,
+};
 
 } // namespace cv
 
 #ifndef CV_8UC3
 #define CV_8UC1 0
 #define CV_8UC3 16
+#endif
+#ifndef CV_8UC4
+#define CV_8UC4 24
 #endif
 #endif

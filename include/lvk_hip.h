@@ -61,7 +61,7 @@ const char* lvk_hip_last_error(lvk_hip_ctx* ctx);    /* NULL ctx: last error of 
 const char* lvk_hip_version(void);                   /* human-readable build string */
 /* ABI number of PART 1 of this header as the library was built (compare with LVK_HIP_ABI_VERSION of the header a host was compiled against;
  * tests/test_abi.py holds the two together). */
-#define LVK_HIP_ABI_VERSION 8
+#define LVK_HIP_ABI_VERSION 9
 int  lvk_hip_abi_version(void);
 /* Devices of this process: contexts are addressed by HIP device index, and lvk_hip_device_count() is the number of indices worth trying -- the
  * highest gfx950 index + 1 (0 when there is no gfx950 device; never an error).  On the usual host every index below it is an MI355X; on a mixed
@@ -406,6 +406,18 @@ int  lvk_hip_deblock_filter_region(const lvk_hip_deblock* deb, int region_xywh[4
  * byte ranges that overlap (in place would race: CAS reads its neighbours).  Asynchronous on the context's stream. */
 int  lvk_hip_cas(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, int format, void* d_dst, int dst_step, float sharpness);
 
+/* ---- format conversion --------------------------------------------------------------------------------------------------------------
+ * VideoFrame::reformatTo (Data/VideoFrame.cpp:170-301; OpenCV's CPU 8-bit cvtColor): d_dst = the d_src frame of format src_format
+ * converted to dst_format, OUT OF PLACE, both packed (LVK_FORMAT_BGR, _RGB, _YUV: 3 channels; _BGRA, _RGBA: 4; _GRAY: 1).  Integer
+ * arithmetic, bit-exact: grey is RGB2Gray<uchar> (15-bit), YUV is RGB2YCrCb_i / YCrCb2RGB_i<uchar> with the YUV coefficients (14-bit),
+ * BGRA / RGBA -> YUV goes through the 3-channel frame, YUV -> GRAY is channel 0, GRAY -> YUV is (g, 128, 128), BGRA <-> RGBA keeps the alpha, and an added
+ * alpha is 255 (YUV -> BGRA / RGBA included: the reference's own call leaves its destination stale, VideoFrame.cpp:262,264).  src_format == dst_format
+ * is a 2-D copy.  Only the cols * channels bytes of each destination row are written (any pitch, any byte alignment).  Refused with
+ * LVK_HIP_ERR_ARG, the destination untouched: an unknown format, rows or cols <= 0, a step < cols * channels, a NULL pointer, and source
+ * and destination byte ranges that overlap.  Asynchronous on the context's stream. */
+int  lvk_hip_reformat(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, int src_format, void* d_dst, int dst_step,
+                      int dst_format);
+
 
 /* =====================================================================================================================================
  * PART 2 -- EXPERIMENTAL / DIAGNOSTICS  (no ABI promise: per-stage entry points of the parity tests, taps, profiling, device look-ahead)
@@ -553,6 +565,14 @@ int lvk_hip_deblock_get_grid(lvk_hip_deblock* deb, uint8_t* mean, uint8_t* grid,
 /* CAS host constant (CasSetup's const1.x, float32, each operation rounded on its own): peak = -(1 / (5 s + ((-8) s + 8))) with
  * s = clamp(sharpness, 0, 1).  Needs no device.  LVK_HIP_ERR_ARG for a NaN sharpness or a NULL peak. */
 int lvk_hip_cas_const(float sharpness, float* peak);
+
+/* ConversionFilter's table (Filters/ConversionFilter.cpp:46-57): the LVK_FORMAT_* that cvtColor(code, dcn) makes of a src_format frame, or -1
+ * when the combination is refused.  Codes (OpenCV's values): BGR2BGRA 0 (= RGB2RGBA), BGRA2BGR 1, BGR2RGBA 2, RGBA2BGR 3, BGR2RGB 4,
+ * BGRA2RGBA 5, BGR2GRAY 6, RGB2GRAY 7, GRAY2BGR 8, GRAY2BGRA 9, BGRA2GRAY 10, RGBA2GRAY 11, BGR2YUV 82, RGB2YUV 83, YUV2BGR 84, YUV2RGB 85;
+ * any other code is refused.  An aliased code takes both of its source formats; BGR2YUV / RGB2YUV and the *2GRAY codes also take the frame
+ * of the same channel order with the other channel count (OpenCV's scn = 3 or 4).  dcn is 0 or the code's destination channel count;
+ * YUV2BGR / YUV2RGB also take dcn 4 (BGRA / RGBA).  Needs no device. */
+int lvk_hip_cvt_code_target(int code, int src_format, int dcn);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ from .context import Context, LvkHipError
 from .stabilization import StabilizationFilter, StabilizationFilterSettings
 from .deblocking import DeblockingFilter, DeblockingFilterSettings
 from .cas import CASFilter
+from .convert import ConversionFilter, reformat
 from . import shard
 
 __all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "CASFilter",
-           "_native"]
+           "ConversionFilter", "reformat", "_native"]

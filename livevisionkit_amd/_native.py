@@ -120,6 +120,8 @@ _SIG = {
     "lvk_hip_deblock_get_grid": (_c.c_int, [_P, _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_float), _c.c_int, _c.POINTER(_c.c_int)]),
     "lvk_hip_cas": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
     "lvk_hip_cas_const": (_c.c_int, [_c.c_float, _c.POINTER(_c.c_float)]),
+    "lvk_hip_reformat": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int]),
+    "lvk_hip_cvt_code_target": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
 }
 
 _lib = None
