@@ -1025,3 +1025,6 @@ using GridDetectorSettings = FeatureDetectorSettings;
 
 // Filters/ConversionFilter.hpp
 #include "ConversionFilter.hpp"
+
+// the OBS plugin's FSR filter (Sources/Scaling/FSRFilter.cpp, Effects/FSREffect.cpp)
+#include "FSRFilter.hpp"

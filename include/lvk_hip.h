@@ -61,7 +61,7 @@ const char* lvk_hip_last_error(lvk_hip_ctx* ctx);    /* NULL ctx: last error of 
 const char* lvk_hip_version(void);                   /* human-readable build string */
 /* ABI number of PART 1 of this header as the library was built (compare with LVK_HIP_ABI_VERSION of the header a host was compiled against;
  * tests/test_abi.py holds the two together). */
-#define LVK_HIP_ABI_VERSION 9
+#define LVK_HIP_ABI_VERSION 10
 int  lvk_hip_abi_version(void);
 /* Devices of this process: contexts are addressed by HIP device index, and lvk_hip_device_count() is the number of indices worth trying -- the
  * highest gfx950 index + 1 (0 when there is no gfx950 device; never an error).  On the usual host every index below it is an MI355X; on a mixed
@@ -418,6 +418,27 @@ int  lvk_hip_cas(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, in
 int  lvk_hip_reformat(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, int src_format, void* d_dst, int dst_step,
                       int dst_format);
 
+/* ---- FSR scaling ------------------------------------------------------------------------------------------------------------------
+ * The OBS plugin's FSR filter (Sources/Scaling/FSRFilter.cpp, Effects/FSREffect.cpp, the FidelityFX FSR 1 EASU pass of fsr.effect; no
+ * RCAS: chain lvk_hip_cas): d_dst (out_rows x out_cols) = EASU of the region (x, y, w, h) of d_src, OUT OF PLACE, for any output size (up,
+ * down, anisotropic).  Taps at the region's edge read the frame outside it; taps outside the frame read its edge (clamp-to-edge).  Packed
+ * frames of format LVK_FORMAT_BGR, _RGB or _YUV (3 channels) or LVK_FORMAT_BGRA, _RGBA (4 channels; the 4th byte is written as 255); the
+ * luma weighs red, green and blue (bytes 0, 1, 2 of YUV).  Only the out_cols * channels bytes of each destination row are written (any
+ * pitch, any byte alignment).  Refused with LVK_HIP_ERR_ARG, the destination untouched: GRAY or unknown formats, rows, cols, out_rows or
+ * out_cols <= 0, a region that is empty or not inside the frame, a step smaller than its row, a NULL pointer, and source and destination
+ * byte ranges that overlap.  Asynchronous on the context's stream. */
+int  lvk_hip_fsr_easu(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, int format, const int region_xywh[4], void* d_dst,
+                      int dst_step, int out_rows, int out_cols);
+/* FSRFilter::tick + FSREffect::should_skip + OBSEffect::is_renderable: the region and output size of a rows x cols frame, host only.
+ * out_rows = out_cols = 0 selects source x multiplier (cvRound(float(size) * multiplier), half to even); otherwise the output is explicit.
+ * crop_ltrb = (left, top, right, bottom) is used iff left + right < cols and top + bottom < rows, else the region is the whole frame.
+ * maintain_aspect_ratio: s = min(out_cols / w, out_rows / h) in float, output = cvRound(w s) x cvRound(h s).  Each output dimension is then
+ * capped at 4096.  *skip = 1 when an output dimension is <= 0, or when output == frame size and the region is the whole frame: the filter
+ * passes such a frame through unchanged.  LVK_HIP_ERR_ARG: rows or cols <= 0, a negative out size, a crop outside [0, 4096], a multiplier
+ * that is not > 0 (when used), a NULL pointer. */
+int  lvk_hip_fsr_geometry(int rows, int cols, int out_rows, int out_cols, float multiplier, int maintain_aspect_ratio, const int crop_ltrb[4],
+                          int region_xywh[4], int out_rows_cols[2], int* skip);
+
 
 /* =====================================================================================================================================
  * PART 2 -- EXPERIMENTAL / DIAGNOSTICS  (no ABI promise: per-stage entry points of the parity tests, taps, profiling, device look-ahead)
@@ -573,6 +594,14 @@ int lvk_hip_cas_const(float sharpness, float* peak);
  * of the same channel order with the other channel count (OpenCV's scn = 3 or 4).  dcn is 0 or the code's destination channel count;
  * YUV2BGR / YUV2RGB also take dcn 4 (BGRA / RGBA).  Needs no device. */
 int lvk_hip_cvt_code_target(int code, int src_format, int dcn);
+
+/* FSR host constants (FsrEasuCon on the CPU, float32, each operation rounded on its own, rcp = 1 / x): con[0..15] = con0 .. con3 for a
+ * rw x rh viewport of a W x H input scaled to ow x oh.  Needs no device.  LVK_HIP_ERR_ARG for a size <= 0 or a NULL con. */
+int lvk_hip_fsr_easu_const(int rw, int rh, int W, int H, int ow, int oh, float con[16]);
+
+/* The kernel path lvk_hip_fsr_easu takes for a rw x rh region scaled to out_rows x out_cols: 0 = staged (the tile's source footprint in
+ * LDS), 1 = direct (taps read from the frame; downscales whose footprint does not fit).  Needs no device.  LVK_HIP_ERR_ARG for a size <= 0. */
+int lvk_hip_fsr_easu_path(int rw, int rh, int out_rows, int out_cols);
 
 #ifdef __cplusplus
 }

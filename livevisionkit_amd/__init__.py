@@ -10,7 +10,8 @@ from .stabilization import StabilizationFilter, StabilizationFilterSettings
 from .deblocking import DeblockingFilter, DeblockingFilterSettings
 from .cas import CASFilter
 from .convert import ConversionFilter, reformat
+from .fsr import FSRFilter, fsr_geometry, easu_const
 from . import shard
 
 __all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "CASFilter",
-           "ConversionFilter", "reformat", "_native"]
+           "ConversionFilter", "reformat", "FSRFilter", "fsr_geometry", "easu_const", "_native"]

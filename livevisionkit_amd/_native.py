@@ -122,6 +122,11 @@ _SIG = {
     "lvk_hip_cas_const": (_c.c_int, [_c.c_float, _c.POINTER(_c.c_float)]),
     "lvk_hip_reformat": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int]),
     "lvk_hip_cvt_code_target": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_fsr_easu": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _P, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_fsr_geometry": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
+                                        _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "lvk_hip_fsr_easu_const": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)]),
+    "lvk_hip_fsr_easu_path": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
 }
 
 _lib = None

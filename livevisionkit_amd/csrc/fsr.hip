@@ -1,0 +1,368 @@
+// The OBS plugin's FSR filter (FSRFilter / FSREffect: the FidelityFX FSR 1 EASU pass of fsr.effect, point-sampled gathers, no RCAS) on
+// the MI355X, out of place from a crop region of a packed 3- or 4-channel frame to an output of any size.  Specification: tests/np_fsr.py
+// and DESIGN.md section 16.
+//
+// One kernel, k_fsr_easu<C, kStaged>, on the context's stream.  A block of 256 threads owns a 64 x 16 pixel output tile; lane l of wave w
+// computes column l of rows 4w .. 4w + 3.  The texel of a tap is (fp.x + rx + dx, fp.y + ry + dy), dx, dy in -1 .. 2, clamped to the frame:
+// the shader's point sampler picks exactly that texel (declared choice 6, pinned by tests/test_fsr_spec.py), so no texture coordinate is
+// formed here.  Two ways to fetch a tap, chosen per launch by the host from the scale:
+//   staged   the tile's source footprint (its fp range plus the -1 .. 2 taps) is read once into LDS as float4 (r, g, b, luma): each texel
+//            is converted and its luma computed once, not once per tap.  Used when the largest footprint of the launch fits kStagePixels.
+//   direct   each tap reads its bytes from the frame and computes its luma (downscales whose footprint does not fit).
+// The arithmetic is the specification's, unfused, with the FidelityFX bit tricks and a correctly rounded 1 / aW.  Output bytes are
+// stored one channel at a time (a whole dword for 4-channel pixels at an aligned address): no byte outside out_cols * C of a row is written.
+#include "lvk_hip_internal.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+namespace {
+
+constexpr int kTileW = 64;                 // output columns per tile (one per lane)
+constexpr int kTileH = 16;                 // output rows per tile (4 per wave)
+constexpr int kRowsPerWave = kTileH / 4;
+constexpr int kStagePixels = 2560;         // LDS budget of the staged path: 40 KiB of float4, four blocks per CU
+
+struct EasuArgs
+{
+    const uint8_t* src;
+    long long src_step;
+    int rows, cols;                        // the frame
+    int rx, ry;                            // the region's origin
+    uint8_t* dst;
+    long long dst_step;
+    int out_rows, out_cols;
+    float c0x, c0y, c0z, c0w;              // FsrEasuCon's con0 (con1 .. con3 only place the texels, which are integers here)
+    int ri, bi;                            // byte of the shader's r and b (g is byte 1)
+};
+
+__device__ __forceinline__ float as_f(uint32_t u) { return __uint_as_float(u); }
+__device__ __forceinline__ uint32_t as_u(float f) { return __float_as_uint(f); }
+__device__ __forceinline__ float lo_rcp(float v) { return as_f(0x7ef07ebbu - as_u(v)); }
+__device__ __forceinline__ float lo_rsq(float v) { return as_f(0x5f347d74u - (as_u(v) >> 1)); }
+__device__ __forceinline__ float sat(float v) { return __builtin_fminf(__builtin_fmaxf(v, 0.0f), 1.0f); }
+
+// correctly rounded u / 255 (the CAS load, tests/test_cas_spec.py checks the correction for all 256 values)
+__device__ __forceinline__ float unit_of(uint32_t u)
+{
+    const float c = 1.0f / 255.0f, x = (float)u;
+    const float q = x * c;
+    return __builtin_fmaf(__builtin_fmaf(-q, 255.0f, x), c, q);
+}
+
+// (r, g, b, luma) of the texel at byte p of the frame
+__device__ __forceinline__ float4 texel(const uint8_t* p, int ri, int bi)
+{
+    const float r = unit_of(p[ri]), g = unit_of(p[1]), b = unit_of(p[bi]);
+    return make_float4(r, g, b, b * 0.5f + (r * 0.5f + g));
+}
+
+// FsrEasuSetF: one bilinear corner's contribution to the direction and the length
+__device__ __forceinline__ void easu_set(float& dirx, float& diry, float& len, float w, float lA, float lB, float lC, float lD, float lE)
+{
+    const float dc = lD - lC, cb = lC - lB;
+    float lenx = lo_rcp(__builtin_fmaxf(__builtin_fabsf(dc), __builtin_fabsf(cb)));
+    const float dx = lD - lB;
+    dirx = dirx + dx * w;
+    lenx = sat(__builtin_fabsf(dx) * lenx);
+    lenx = lenx * lenx;
+    len = len + lenx * w;
+    const float ec = lE - lC, ca = lC - lA;
+    float leny = lo_rcp(__builtin_fmaxf(__builtin_fabsf(ec), __builtin_fabsf(ca)));
+    const float dy = lE - lA;
+    diry = diry + dy * w;
+    leny = sat(__builtin_fabsf(dy) * leny);
+    leny = leny * leny;
+    len = len + leny * w;
+}
+
+// FsrEasuTapF for the tap at (ox, oy) from 'f'
+__device__ __forceinline__ void easu_tap(float3& ac, float& aw, float ox, float oy, float ppx, float ppy, float dirx, float diry, float len2x,
+                                         float len2y, float lob, float clp, float4 c)
+{
+    const float offx = ox - ppx, offy = oy - ppy;
+    float vx = (offx * dirx) + (offy * diry);
+    float vy = (offx * (-diry)) + (offy * dirx);
+    vx = vx * len2x;
+    vy = vy * len2y;
+    const float d2 = __builtin_fminf(vx * vx + vy * vy, clp);
+    float wb = 0.4f * d2 + -1.0f;
+    float wa = lob * d2 + -1.0f;
+    wb = wb * wb;
+    wa = wa * wa;
+    wb = 1.5625f * wb + -0.5625f;
+    const float w = wb * wa;
+    ac.x = ac.x + c.x * w;
+    ac.y = ac.y + c.y * w;
+    ac.z = ac.z + c.z * w;
+    aw = aw + w;
+}
+
+// FsrEasuF from the 12 taps t[dy + 1][dx + 1] (dx, dy in -1 .. 2; the four corners are not used) and the fraction (ppx, ppy) of pp
+__device__ __forceinline__ float3 easu(const float4 (&t)[4][4], float ppx, float ppy)
+{
+    const float4 b = t[0][1], c = t[0][2], e = t[1][0], f = t[1][1], g = t[1][2], h = t[1][3];
+    const float4 i = t[2][0], j = t[2][1], k = t[2][2], l = t[2][3], n = t[3][1], o = t[3][2];
+    float dirx = 0.0f, diry = 0.0f, len = 0.0f;
+    easu_set(dirx, diry, len, (1.0f - ppx) * (1.0f - ppy), b.w, e.w, f.w, g.w, j.w);
+    easu_set(dirx, diry, len, ppx * (1.0f - ppy), c.w, f.w, g.w, h.w, k.w);
+    easu_set(dirx, diry, len, (1.0f - ppx) * ppy, f.w, i.w, j.w, k.w, n.w);
+    easu_set(dirx, diry, len, ppx * ppy, g.w, j.w, k.w, l.w, o.w);
+    const float dir2x = dirx * dirx, dir2y = diry * diry;
+    float dirr = dir2x + dir2y;
+    const bool zro = dirr < (1.0f / 32768.0f);
+    dirr = zro ? 1.0f : lo_rsq(dirr);
+    dirx = zro ? 1.0f : dirx;
+    dirx = dirx * dirr;
+    diry = diry * dirr;
+    len = len * 0.5f;
+    len = len * len;
+    const float stretch = (dirx * dirx + diry * diry) * lo_rcp(__builtin_fmaxf(__builtin_fabsf(dirx), __builtin_fabsf(diry)));
+    const float len2x = 1.0f + (stretch - 1.0f) * len;
+    const float len2y = 1.0f + -0.5f * len;
+    const float lob = 0.5f + -0.29f * len;             // (float)((1/4 - 0.04) - 0.5)
+    const float clp = lo_rcp(lob);
+    float3 ac = make_float3(0.0f, 0.0f, 0.0f);
+    float aw = 0.0f;
+    easu_tap(ac, aw, 0.0f, -1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, b);
+    easu_tap(ac, aw, 1.0f, -1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, c);
+    easu_tap(ac, aw, -1.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, i);
+    easu_tap(ac, aw, 0.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, j);
+    easu_tap(ac, aw, 0.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, f);
+    easu_tap(ac, aw, -1.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, e);
+    easu_tap(ac, aw, 1.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, k);
+    easu_tap(ac, aw, 2.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, l);
+    easu_tap(ac, aw, 2.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, h);
+    easu_tap(ac, aw, 1.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, g);
+    easu_tap(ac, aw, 1.0f, 2.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, o);
+    easu_tap(ac, aw, 0.0f, 2.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, n);
+    const float inv = 1.0f / aw;                       // correctly rounded (ARcpF1 on OpenGL)
+    const float mnr = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.x, g.x), j.x), k.x);
+    const float mng = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.y, g.y), j.y), k.y);
+    const float mnb = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.z, g.z), j.z), k.z);
+    const float mxr = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(f.x, g.x), j.x), k.x);
+    const float mxg = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(f.y, g.y), j.y), k.y);
+    const float mxb = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(f.z, g.z), j.z), k.z);
+    return make_float3(__builtin_fminf(mxr, __builtin_fmaxf(mnr, ac.x * inv)), __builtin_fminf(mxg, __builtin_fmaxf(mng, ac.y * inv)),
+                       __builtin_fminf(mxb, __builtin_fmaxf(mnb, ac.z * inv)));
+}
+
+__device__ __forceinline__ uint32_t to_byte(float v) { return (uint32_t)rintf(v * 255.0f); }
+
+template <int C>
+__device__ __forceinline__ void store_pixel(const EasuArgs& a, int x, int y, float3 pix)
+{
+    uint8_t* p = a.dst + (long long)y * a.dst_step + (long long)x * C;
+    const uint32_t r = to_byte(pix.x), g = to_byte(pix.y), b = to_byte(pix.z);
+    if (C == 4 && ((uintptr_t)p & 3) == 0)
+    {
+        *(uint32_t*)p = (r << (8 * a.ri)) | (g << 8) | (b << (8 * a.bi)) | 0xff000000u;
+        return;
+    }
+    p[a.ri] = (uint8_t)r;
+    p[1] = (uint8_t)g;
+    p[a.bi] = (uint8_t)b;
+    if (C == 4) p[3] = 255;
+}
+
+__device__ __forceinline__ float pp_of(int ip, float scale, float bias) { return (float)ip * scale + bias; }
+
+template <int C, bool kStaged>
+__global__ __launch_bounds__(256)
+void k_fsr_easu(EasuArgs a)
+{
+    __shared__ float4 stage[kStaged ? kStagePixels : 1];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = blockIdx.x * kTileW;
+    const int x = x0 + lane;
+    const float ppx_full = pp_of(x, a.c0x, a.c0z);
+    const float fpx = floorf(ppx_full), ppx = ppx_full - fpx;
+    const int fx = (int)fpx;
+    // the tile's first and last fp.x: pp grows with x, and rounding keeps that order
+    const int fx0 = (int)floorf(pp_of(x0, a.c0x, a.c0z));
+    const int fx1 = (int)floorf(pp_of(min(x0 + kTileW, a.out_cols) - 1, a.c0x, a.c0z));
+    const int sw = fx1 - fx0 + 4;                                  // staged columns: fp.x - 1 .. fp.x + 2
+
+    for (int y0 = blockIdx.y * kTileH; y0 < a.out_rows; y0 += gridDim.y * kTileH)
+    {
+        int fy0 = 0;
+        if (kStaged)
+        {
+            fy0 = (int)floorf(pp_of(y0, a.c0y, a.c0w));
+            const int fy1 = (int)floorf(pp_of(min(y0 + kTileH, a.out_rows) - 1, a.c0y, a.c0w));
+            const int sh = fy1 - fy0 + 4;
+            for (int k = tid; k < sw * sh; k += 256)
+            {
+                const int ty = k / sw, tx = k - ty * sw;
+                const int sx = min(max(fx0 - 1 + a.rx + tx, 0), a.cols - 1);
+                const int sy = min(max(fy0 - 1 + a.ry + ty, 0), a.rows - 1);
+                stage[k] = texel(a.src + (long long)sy * a.src_step + (long long)sx * C, a.ri, a.bi);
+            }
+            __syncthreads();
+        }
+        if (x < a.out_cols)
+        {
+#pragma unroll 1
+            for (int j = 0; j < kRowsPerWave; j++)
+            {
+                const int y = y0 + wave * kRowsPerWave + j;
+                if (y >= a.out_rows) break;
+                const float ppy_full = pp_of(y, a.c0y, a.c0w);
+                const float fpy = floorf(ppy_full), ppy = ppy_full - fpy;
+                const int fy = (int)fpy;
+                float4 t[4][4];
+                if (kStaged)
+                {
+                    const float4* s = stage + (fy - fy0) * sw + (fx - fx0);
+#pragma unroll
+                    for (int dy = 0; dy < 4; dy++)
+#pragma unroll
+                        for (int dx = 0; dx < 4; dx++)
+                            if ((dy == 0 || dy == 3) && (dx == 0 || dx == 3)) t[dy][dx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                            else t[dy][dx] = s[dy * sw + dx];
+                }
+                else
+                {
+                    int cx[4];
+#pragma unroll
+                    for (int dx = 0; dx < 4; dx++) cx[dx] = min(max(fx + a.rx + dx - 1, 0), a.cols - 1);
+#pragma unroll
+                    for (int dy = 0; dy < 4; dy++)
+                    {
+                        const int sy = min(max(fy + a.ry + dy - 1, 0), a.rows - 1);
+                        const uint8_t* row = a.src + (long long)sy * a.src_step;
+#pragma unroll
+                        for (int dx = 0; dx < 4; dx++)
+                            if ((dy == 0 || dy == 3) && (dx == 0 || dx == 3)) t[dy][dx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                            else t[dy][dx] = texel(row + (long long)cx[dx] * C, a.ri, a.bi);
+                    }
+                }
+                store_pixel<C>(a, x, y, easu(t, ppx, ppy));
+            }
+        }
+        if (kStaged) __syncthreads();                               // the stage is reused by the next row of tiles
+    }
+}
+
+bool fsr_format_channels(int format, int* channels)
+{
+    switch (format)
+    {
+    case LVK_FORMAT_BGR: case LVK_FORMAT_RGB: case LVK_FORMAT_YUV: *channels = 3; return true;
+    case LVK_FORMAT_BGRA: case LVK_FORMAT_RGBA: *channels = 4; return true;
+    default: return false;
+    }
+}
+
+// The largest fp span (last - first + 1) of any kTile-sized run of outputs 0 .. n - 1, with the kernel's float32 arithmetic.
+int max_fp_span(int n, int tile, float scale, float bias)
+{
+    int worst = 0;
+    for (int i0 = 0; i0 < n; i0 += tile)
+    {
+        const int i1 = std::min(i0 + tile, n) - 1;
+        const int f0 = (int)std::floor((float)i0 * scale + bias), f1 = (int)std::floor((float)i1 * scale + bias);
+        worst = std::max(worst, f1 - f0 + 1);
+    }
+    return worst;
+}
+
+// cvRound of a float32 (round half to even), saturating far beyond the output cap
+int cv_round(float v) { return v >= 1.0e9f ? 1000000000 : (int)std::nearbyint(v); }
+
+} // namespace
+
+extern "C" {
+
+int lvk_hip_fsr_easu_const(int rw, int rh, int W, int H, int ow, int oh, float con[16])
+{
+    if (!con || rw <= 0 || rh <= 0 || W <= 0 || H <= 0 || ow <= 0 || oh <= 0) return LVK_HIP_ERR_ARG;
+    // FsrEasuCon on the CPU, each float operation rounded on its own (-ffp-contract=off); rcp is 1 / x
+    const float frw = (float)rw, frh = (float)rh, rW = 1.0f / (float)W, rH = 1.0f / (float)H, row = 1.0f / (float)ow, roh = 1.0f / (float)oh;
+    const float v[16] = {frw * row, frh * roh, (0.5f * frw) * row - 0.5f, (0.5f * frh) * roh - 0.5f,
+                         rW, rH, 1.0f * rW, -1.0f * rH,
+                         -1.0f * rW, 2.0f * rH, 1.0f * rW, 2.0f * rH,
+                         0.0f * rW, 4.0f * rH, 0.0f, 0.0f};
+    std::copy(v, v + 16, con);
+    return LVK_HIP_OK;
+}
+
+int lvk_hip_fsr_easu_path(int rw, int rh, int out_rows, int out_cols)
+{
+    float con[16];
+    if (lvk_hip_fsr_easu_const(rw, rh, 1, 1, out_cols, out_rows, con) != LVK_HIP_OK) return LVK_HIP_ERR_ARG;
+    const long long sw = max_fp_span(out_cols, kTileW, con[0], con[2]) + 3LL, sh = max_fp_span(out_rows, kTileH, con[1], con[3]) + 3LL;
+    return sw * sh <= kStagePixels ? 0 : 1;
+}
+
+int lvk_hip_fsr_geometry(int rows, int cols, int out_rows, int out_cols, float multiplier, int maintain_aspect_ratio, const int crop_ltrb[4],
+                         int region_xywh[4], int out_rows_cols[2], int* skip)
+{
+    if (rows <= 0 || cols <= 0 || out_rows < 0 || out_cols < 0 || !crop_ltrb || !region_xywh || !out_rows_cols || !skip) return LVK_HIP_ERR_ARG;
+    for (int k = 0; k < 4; k++)
+        if (crop_ltrb[k] < 0 || crop_ltrb[k] > 4096) return LVK_HIP_ERR_ARG;
+    const bool by_multiplier = out_rows == 0 && out_cols == 0;
+    if (by_multiplier && !(multiplier > 0.0f && std::isfinite(multiplier))) return LVK_HIP_ERR_ARG;
+    // FSRFilter::tick: the output size ...
+    int ow = out_cols, oh = out_rows;
+    if (by_multiplier) { ow = cv_round((float)cols * multiplier); oh = cv_round((float)rows * multiplier); }
+    // ... the crop region ...
+    const int l = crop_ltrb[0], t = crop_ltrb[1], r = crop_ltrb[2], b = crop_ltrb[3];
+    int rx = 0, ry = 0, rw = cols, rh = rows;
+    if (l + r < cols && t + b < rows) { rx = l; ry = t; rw = cols - r - l; rh = rows - b - t; }
+    // ... the aspect-ratio fit and the 4096 cap
+    if (maintain_aspect_ratio && (long long)rw * rh != 0)
+    {
+        const float s = std::min((float)ow / (float)rw, (float)oh / (float)rh);
+        ow = cv_round((float)rw * s);
+        oh = cv_round((float)rh * s);
+    }
+    ow = std::min(ow, 4096);
+    oh = std::min(oh, 4096);
+    region_xywh[0] = rx; region_xywh[1] = ry; region_xywh[2] = rw; region_xywh[3] = rh;
+    out_rows_cols[0] = oh; out_rows_cols[1] = ow;
+    // OBSEffect::is_renderable + FSREffect::should_skip (the region is inside the frame and not empty by construction)
+    *skip = (ow <= 0 || oh <= 0 || (ow == cols && oh == rows && rw == cols && rh == rows)) ? 1 : 0;
+    return LVK_HIP_OK;
+}
+
+int lvk_hip_fsr_easu(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, int format, const int region_xywh[4], void* d_dst,
+                     int dst_step, int out_rows, int out_cols)
+{
+    LVK_HIP_ENTRY(ctx);
+    int ch = 0;
+    if (!fsr_format_channels(format, &ch)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: packed BGR / RGB / YUV / BGRA / RGBA frames only");
+    LVK_HIP_REQUIRE(ctx, d_src && d_dst && region_xywh && rows > 0 && cols > 0 && out_rows > 0 && out_cols > 0);
+    const int rx = region_xywh[0], ry = region_xywh[1], rw = region_xywh[2], rh = region_xywh[3];
+    if (!(rx >= 0 && ry >= 0 && rw > 0 && rh > 0 && (long long)rx + rw <= cols && (long long)ry + rh <= rows))
+        return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: the region must be a non-empty rectangle inside the frame");
+    const long long src_row = (long long)cols * ch, dst_row = (long long)out_cols * ch;
+    LVK_HIP_REQUIRE(ctx, (long long)src_step >= src_row && (long long)dst_step >= dst_row);
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((long long)(rows - 1) * src_step + src_row);
+    const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uintptr_t)((long long)(out_rows - 1) * dst_step + dst_row);
+    if (s0 < t1 && t0 < s1) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: the source and destination overlap");
+
+    float con[16];
+    lvk_hip_fsr_easu_const(rw, rh, cols, rows, out_cols, out_rows, con);
+    const bool bgr = format == LVK_FORMAT_BGR || format == LVK_FORMAT_BGRA;
+    const EasuArgs a{(const uint8_t*)d_src, (long long)src_step, rows, cols, rx, ry, (uint8_t*)d_dst, (long long)dst_step, out_rows, out_cols,
+                     con[0], con[1], con[2], con[3], bgr ? 2 : 0, bgr ? 0 : 2};
+    const bool staged = lvk_hip_fsr_easu_path(rw, rh, out_rows, out_cols) == 0;
+    const dim3 grid((unsigned)((out_cols + kTileW - 1) / kTileW), (unsigned)std::min((out_rows + kTileH - 1) / kTileH, 65535));
+    if (ch == 3)
+    {
+        if (staged) hipLaunchKernelGGL((k_fsr_easu<3, true>), grid, dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_fsr_easu<3, false>), grid, dim3(256), 0, ctx->stream, a);
+    }
+    else
+    {
+        if (staged) hipLaunchKernelGGL((k_fsr_easu<4, true>), grid, dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_fsr_easu<4, false>), grid, dim3(256), 0, ctx->stream, a);
+    }
+    LVK_HIP_CHECK(ctx, hipGetLastError());
+    return LVK_HIP_OK;
+}
+
+} // extern "C"
