@@ -14,10 +14,10 @@ struct CASFilterSettings
     float sharpness = 0.8f;          // [0, 1] (CASFilter.cpp: PROP_SHARPNESS_DEFAULT; CASEffect.cpp: LVK_ASSERT_01)
 };
 
-class CASFilter final : public VideoFilter, public Configurable<CASFilterSettings>
+class CASFilter final : public detail::ContextFilter, public Configurable<CASFilterSettings>
 {
 public:
-    explicit CASFilter(const CASFilterSettings& settings = {}) : VideoFilter("CAS Filter") { configure(settings); }
+    explicit CASFilter(const CASFilterSettings& settings = {}) : ContextFilter("CAS Filter") { configure(settings); }
     CASFilter(const CASFilter&) = delete;
     CASFilter& operator=(const CASFilter&) = delete;
 
@@ -28,30 +28,20 @@ public:
     }
 
 private:
-    // frames of another context (a chain whose stages run on different streams) are fenced in both directions around the filter's work
-    void fence_in(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) m_Ctx->wait_for(*frame.context()); }
-    void fence_out(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) frame.context()->wait_for(*m_Ctx); }
-
     void filter(VideoFrame&& input, VideoFrame& output) override
     {
         LVK_HIP_ASSERT(!input.empty());
         VideoFrame src = std::move(input);          // CAS reads its neighbours: out of place, into a fresh frame
-        if (!m_Ctx) m_Ctx = src.context();
+        adopt(src);
         VideoFrame dst(src.timestamp);
         dst.create(src.size(), src.type(), m_Ctx);
         dst.format = src.format;
-        {
-            hip::ContextLock lock(m_Ctx->mutex());
-            fence_in(src);
+        run(src, [&] {
             m_Ctx->check(lvk_hip_cas(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, (int)src.format, dst.device_ptr(),
                                      (int)dst.step, m_Settings.sharpness), "CASFilter::filter");
-            fence_out(src);
-        }
+        });
         output = std::move(dst);
     }
-    void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
-
-    std::shared_ptr<hip::Context> m_Ctx;
 };
 
 } // namespace lvk

@@ -19,10 +19,10 @@ struct ConversionFilterSettings
     std::optional<size_t> output_channels;                 // cvtColor's dcn (none: 0, the code's own)
 };
 
-class ConversionFilter final : public VideoFilter, public Configurable<ConversionFilterSettings>
+class ConversionFilter final : public detail::ContextFilter, public Configurable<ConversionFilterSettings>
 {
 public:
-    explicit ConversionFilter(const ConversionFilterSettings& settings = {}) : VideoFilter("Conversion Filter") { configure(settings); }
+    explicit ConversionFilter(const ConversionFilterSettings& settings = {}) : ContextFilter("Conversion Filter") { configure(settings); }
     explicit ConversionFilter(const cv::ColorConversionCodes conversion_code)
         : ConversionFilter(ConversionFilterSettings{conversion_code, std::nullopt}) {}
     ConversionFilter(const ConversionFilter&) = delete;
@@ -44,10 +44,6 @@ public:
 private:
     static int dcn_of(const ConversionFilterSettings& s) { return s.output_channels ? (int)*s.output_channels : 0; }
 
-    // frames of another context (a chain whose stages run on different streams) are fenced in both directions around the filter's work
-    void fence_in(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) m_Ctx->wait_for(*frame.context()); }
-    void fence_out(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) frame.context()->wait_for(*m_Ctx); }
-
     void filter(VideoFrame&& input, VideoFrame& output) override                    // ConversionFilter.cpp:46-57
     {
         LVK_HIP_ASSERT(!input.empty());
@@ -56,22 +52,16 @@ private:
         LVK_HIP_ASSERT(to >= 0);                           // cvtColor would refuse the frame's channel count
         if (to < 0) return;
         VideoFrame src = std::move(input);
-        if (!m_Ctx) m_Ctx = src.context();
+        adopt(src);
         VideoFrame dst(src.timestamp);
         dst.create(src.size(), VideoFrame::type_of((VideoFrame::Format)to), m_Ctx);
         dst.format = (VideoFrame::Format)to;
-        {
-            hip::ContextLock lock(m_Ctx->mutex());
-            fence_in(src);
+        run(src, [&] {
             m_Ctx->check(lvk_hip_reformat(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, (int)src.format, dst.device_ptr(),
                                           (int)dst.step, to), "ConversionFilter::filter");
-            fence_out(src);
-        }
+        });
         output = std::move(dst);
     }
-    void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
-
-    std::shared_ptr<hip::Context> m_Ctx;
 };
 
 } // namespace lvk

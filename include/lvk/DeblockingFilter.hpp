@@ -16,10 +16,10 @@ struct DeblockingFilterSettings                      // Filters/DeblockingFilter
     float filter_scaling = 4;        // Smaller is stronger (1/x)
 };
 
-class DeblockingFilter final : public VideoFilter, public Configurable<DeblockingFilterSettings>
+class DeblockingFilter final : public detail::ContextFilter, public Configurable<DeblockingFilterSettings>
 {
 public:
-    explicit DeblockingFilter(const DeblockingFilterSettings& settings = {}) : VideoFilter("Deblocking Filter") { configure(settings); }
+    explicit DeblockingFilter(const DeblockingFilterSettings& settings = {}) : ContextFilter("Deblocking Filter") { configure(settings); }
     ~DeblockingFilter() override
     {
         if (!m_Handle) return;
@@ -48,11 +48,10 @@ public:
     void draw_influence(VideoFrame& frame) const                                  // DeblockingFilter.cpp:114-131
     {
         LVK_HIP_ASSERT(m_Handle != nullptr && !frame.empty());
-        hip::ContextLock lock(m_Ctx->mutex());
-        fence_in(frame);
-        m_Ctx->check(lvk_hip_deblock_draw_influence(m_Handle, frame.device_ptr(), (int)frame.step, frame.rows, frame.cols, (int)frame.format),
-                     "DeblockingFilter::draw_influence");
-        fence_out(frame);
+        run(frame, [&] {
+            m_Ctx->check(lvk_hip_deblock_draw_influence(m_Handle, frame.device_ptr(), (int)frame.step, frame.rows, frame.cols, (int)frame.format),
+                         "DeblockingFilter::draw_influence");
+        });
     }
 
     cv::Rect filter_region() const                                                // DeblockingFilter.cpp:135-138
@@ -69,9 +68,6 @@ private:
         c.detection_levels = s.detection_levels; c.block_size = s.block_size; c.filter_size = s.filter_size; c.filter_scaling = s.filter_scaling;
         return c;
     }
-    // frames of another context (a chain whose stages run on different streams) are fenced in both directions around the filter's work
-    void fence_in(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) m_Ctx->wait_for(*frame.context()); }
-    void fence_out(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) frame.context()->wait_for(*m_Ctx); }
 
     void filter(VideoFrame&& input, VideoFrame& output) override                  // DeblockingFilter.cpp:48-110, in place
     {
@@ -84,18 +80,13 @@ private:
             hip::ContextLock lock(m_Ctx->mutex());
             m_Ctx->check(lvk_hip_deblock_create(m_Ctx->get(), &s, &m_Handle), "DeblockingFilter");
         }
-        {
-            hip::ContextLock lock(m_Ctx->mutex());
-            fence_in(frame);
+        run(frame, [&] {
             m_Ctx->check(lvk_hip_deblock_apply(m_Handle, frame.device_ptr(), (int)frame.step, frame.rows, frame.cols, (int)frame.format, nullptr),
                          "DeblockingFilter::filter");
-            fence_out(frame);
-        }
+        });
         output = std::move(frame);
     }
-    void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
 
-    std::shared_ptr<hip::Context> m_Ctx;
     lvk_hip_deblock* m_Handle = nullptr;
 };
 

@@ -17,10 +17,10 @@ struct FSRFilterSettings
     int crop_left = 0, crop_top = 0, crop_right = 0, crop_bottom = 0;     // [0, 4096] (PROP_CROP_MIN / PROP_CROP_MAX)
 };
 
-class FSRFilter final : public VideoFilter, public Configurable<FSRFilterSettings>
+class FSRFilter final : public detail::ContextFilter, public Configurable<FSRFilterSettings>
 {
 public:
-    explicit FSRFilter(const FSRFilterSettings& settings = {}) : VideoFilter("FSR Filter") { configure(settings); }
+    explicit FSRFilter(const FSRFilterSettings& settings = {}) : ContextFilter("FSR Filter") { configure(settings); }
     FSRFilter(const FSRFilter&) = delete;
     FSRFilter& operator=(const FSRFilter&) = delete;
 
@@ -38,9 +38,6 @@ public:
 private:
     static bool in_crop_range(int c) { return c >= 0 && c <= 4096; }
 
-    void fence_in(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) m_Ctx->wait_for(*frame.context()); }
-    void fence_out(const VideoFrame& frame) const { if (frame.context() && frame.context() != m_Ctx) frame.context()->wait_for(*m_Ctx); }
-
     void filter(VideoFrame&& input, VideoFrame& output) override
     {
         LVK_HIP_ASSERT(!input.empty());
@@ -55,22 +52,16 @@ private:
             return;
         }
         VideoFrame src = std::move(input);
-        if (!m_Ctx) m_Ctx = src.context();
+        adopt(src);
         VideoFrame dst(src.timestamp);
         dst.create(cv::Size(size[1], size[0]), src.type(), m_Ctx);
         dst.format = src.format;
-        {
-            hip::ContextLock lock(m_Ctx->mutex());
-            fence_in(src);
+        run(src, [&] {
             m_Ctx->check(lvk_hip_fsr_easu(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, (int)src.format, region, dst.device_ptr(),
                                           (int)dst.step, dst.rows, dst.cols), "FSRFilter::filter");
-            fence_out(src);
-        }
+        });
         output = std::move(dst);
     }
-    void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
-
-    std::shared_ptr<hip::Context> m_Ctx;
 };
 
 } // namespace lvk

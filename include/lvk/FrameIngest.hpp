@@ -82,8 +82,8 @@ public:
         const int rows = (int)dst->height, cols = (int)dst->width;
         LVK_HIP_ASSERT(rows == src.rows && cols == src.cols);
         Plane pl[3]; const int n = planes(rows, cols, pl);
+        if (src.context() && src.context() != m_ctx) m_ctx->wait_for(*src.context());     // (both contexts' locks: before ours is held)
         hip::ContextLock lock(m_ctx->mutex());
-        if (src.context() && src.context() != m_ctx) m_ctx->wait_for(*src.context());
         size_t off[3], total = 0;
         for (int i = 0; i < n; i++)
         {

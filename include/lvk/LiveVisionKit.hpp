@@ -560,6 +560,35 @@ private:
 };
 typedef VideoFilter IdentityFilter;
 
+namespace detail {
+// The filters that launch on the context of their first frame (CAS, FSR, Conversion, Deblocking).  A frame of another context (a chain whose
+// stages run on different streams) is fenced in both directions around the launch, with our own lock NOT held: Context::wait_for takes both
+// contexts' locks, so two filters on two threads that feed each other frames of their contexts would otherwise each keep their own mutex
+// while waiting for the other's (round-4 ADVICE).  Fencing out after the lock is released stays correct: whatever is enqueued on our stream
+// in between only makes the producer wait longer.
+class ContextFilter : public VideoFilter
+{
+protected:
+    using VideoFilter::VideoFilter;
+
+    void adopt(const VideoFrame& frame) { if (!m_Ctx) m_Ctx = frame.context(); }      // the first frame's context, never replaced
+    template <typename F>
+    void run(const VideoFrame& src, F&& launch) const
+    {
+        const bool foreign = src.context() && src.context() != m_Ctx;
+        if (foreign) m_Ctx->wait_for(*src.context());
+        {
+            hip::ContextLock lock(m_Ctx->mutex());
+            launch();
+        }
+        if (foreign) src.context()->wait_for(*m_Ctx);
+    }
+    void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
+
+    std::shared_ptr<hip::Context> m_Ctx;
+};
+} // namespace detail
+
 // ---------------------------------------------------------------------------------------------- Filters/StabilizationFilter.hpp
 // Camera profile of the plugin's lens-correction filter (Modules/OBS-Plugin/Sources/Tools/CCTool.cpp:120-153)
 struct CameraParameters { double fx = 0, fy = 0, cx = 0, cy = 0, k1 = 0, k2 = 0, p1 = 0, p2 = 0, k3 = 0; };
@@ -925,11 +954,12 @@ struct ScalingFilterSettings                         // Filters/ScalingFilter.hp
     bool yuv_input = true;
 };
 
-class ScalingFilter final : public VideoFilter, public Configurable<ScalingFilterSettings>   // Filters/ScalingFilter.cpp:27-59
+// (it follows each frame's context: m_Ctx is the last frame's, not an adopted one)
+class ScalingFilter final : public detail::ContextFilter, public Configurable<ScalingFilterSettings>   // Filters/ScalingFilter.cpp:27-59
 {
 public:
-    explicit ScalingFilter(const ScalingFilterSettings& settings = {}) : VideoFilter("Scaling Filter") { configure(settings); }
-    explicit ScalingFilter(const cv::Size& output_size, const float sharpness = 0.8f) : VideoFilter("Scaling Filter")
+    explicit ScalingFilter(const ScalingFilterSettings& settings = {}) : ContextFilter("Scaling Filter") { configure(settings); }
+    explicit ScalingFilter(const cv::Size& output_size, const float sharpness = 0.8f) : ContextFilter("Scaling Filter")
     {
         ScalingFilterSettings settings; settings.output_size = output_size; settings.sharpness = sharpness;
         configure(settings);
@@ -951,8 +981,6 @@ private:
         lvk::sharpen(scaled, output, m_Settings.sharpness);
         output.timestamp = in.timestamp;
     }
-    void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
-    std::shared_ptr<hip::Context> m_Ctx;
 };
 
 // ---------------------------------------------------------------------------------------------- Filters/CompositeFilter.hpp

@@ -6,10 +6,9 @@ import ctypes
 import math
 
 from . import _native
-from .stabilization import FORMAT_BGR
+from .stabilization import CHANNELS, FORMAT_BGR, frame_args, out_frame
 
 _c = ctypes
-_CHANNELS = {0: 3, 2: 3, 4: 3, 1: 4, 3: 4}      # LVK_FORMAT_BGR, _RGB, _YUV; _BGRA, _RGBA
 
 
 def cas_const(sharpness):
@@ -18,13 +17,6 @@ def cas_const(sharpness):
     if _native.load().lvk_hip_cas_const(float(sharpness), _c.byref(peak)) != 0:
         raise ValueError("sharpness must be a number")
     return peak.value
-
-
-def _frame_args(frame, channels):
-    if (frame.dim() != 3 or frame.shape[2] != channels or frame.stride(2) != 1 or frame.stride(1) != channels
-            or frame.dtype.itemsize != 1):
-        raise ValueError("a packed uint8 frame [rows, cols, %d] with contiguous rows is required" % channels)
-    return frame.data_ptr(), frame.stride(0)
 
 
 class CASFilter:
@@ -43,16 +35,12 @@ class CASFilter:
 
     def apply(self, frame, fmt=FORMAT_BGR, out=None):
         """Sharpens `frame` into `out` (a new tensor when None; it must not overlap `frame`); returns `out`."""
-        import torch
-        if fmt not in _CHANNELS:
+        ch = CHANNELS.get(fmt)
+        if ch not in (3, 4):
             raise ValueError("CAS takes BGR / RGB / YUV and BGRA / RGBA frames")
-        ch = _CHANNELS[fmt]
-        src, src_step = _frame_args(frame, ch)
+        src, src_step = frame_args(frame, ch)
         rows, cols = frame.shape[0], frame.shape[1]
-        if out is None:
-            out = torch.empty((rows, cols, ch), dtype=torch.uint8, device=frame.device)
-        if tuple(out.shape) != (rows, cols, ch):
-            raise ValueError("out must have the shape of the frame")
-        dst, dst_step = _frame_args(out, ch)
+        out = out_frame(out, frame, (rows, cols, ch), "out must have the shape of the frame")
+        dst, dst_step = frame_args(out, ch)
         self.ctx._check(self.lib.lvk_hip_cas(self.ctx.handle, src, src_step, rows, cols, int(fmt), dst, dst_step, self.sharpness))
         return out

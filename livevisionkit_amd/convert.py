@@ -6,10 +6,9 @@ DESIGN.md section 15."""
 import ctypes
 
 from . import _native
-from .stabilization import FORMAT_BGR, FORMAT_BGRA, FORMAT_RGB, FORMAT_RGBA, FORMAT_YUV, FORMAT_GRAY
+from .stabilization import CHANNELS, FORMAT_BGR, frame_args, out_frame
 
 _c = ctypes
-CHANNELS = {FORMAT_BGR: 3, FORMAT_BGRA: 4, FORMAT_RGB: 3, FORMAT_RGBA: 4, FORMAT_YUV: 3, FORMAT_GRAY: 1}
 
 # cv::ColorConversionCodes (OpenCV's values) that ConversionFilter takes
 COLOR_BGR2BGRA = COLOR_RGB2RGBA = 0
@@ -30,26 +29,15 @@ def code_target(code, src_fmt, dcn=0):
     return _native.load().lvk_hip_cvt_code_target(int(code), int(src_fmt), int(dcn))
 
 
-def _frame_args(frame, channels):
-    if (frame.dim() != 3 or frame.shape[2] != channels or frame.stride(2) != 1 or frame.stride(1) != channels
-            or frame.dtype.itemsize != 1):
-        raise ValueError("a packed uint8 frame [rows, cols, %d] with contiguous rows is required" % channels)
-    return frame.data_ptr(), frame.stride(0)
-
-
 def reformat(ctx, frame, src_fmt, dst_fmt, out=None):
     """VideoFrame::reformatTo: `frame` (format src_fmt) converted to dst_fmt into `out` (a new tensor when None; it must not overlap
     `frame`); returns `out`.  The same format on both sides is a copy."""
-    import torch
     if src_fmt not in CHANNELS or dst_fmt not in CHANNELS:
         raise ValueError("formats are FORMAT_BGR .. FORMAT_GRAY")
-    src, src_step = _frame_args(frame, CHANNELS[src_fmt])
+    src, src_step = frame_args(frame, CHANNELS[src_fmt])
     rows, cols, dc = frame.shape[0], frame.shape[1], CHANNELS[dst_fmt]
-    if out is None:
-        out = torch.empty((rows, cols, dc), dtype=torch.uint8, device=frame.device)
-    if tuple(out.shape) != (rows, cols, dc):
-        raise ValueError("out must be [rows, cols, %d]" % dc)
-    dst, dst_step = _frame_args(out, dc)
+    out = out_frame(out, frame, (rows, cols, dc), "out must be [rows, cols, %d]" % dc)
+    dst, dst_step = frame_args(out, dc)
     ctx._check(ctx.lib.lvk_hip_reformat(ctx.handle, src, src_step, rows, cols, int(src_fmt), dst, dst_step, int(dst_fmt)))
     return out
 

@@ -173,16 +173,6 @@ void k_cas(const uint8_t* __restrict__ src, long long src_step, int rows, int co
     }
 }
 
-bool cas_format_channels(int format, int* channels)
-{
-    switch (format)
-    {
-    case LVK_FORMAT_BGR: case LVK_FORMAT_RGB: case LVK_FORMAT_YUV: *channels = 3; return true;
-    case LVK_FORMAT_BGRA: case LVK_FORMAT_RGBA: *channels = 4; return true;
-    default: return false;
-    }
-}
-
 } // namespace
 
 extern "C" {
@@ -200,16 +190,14 @@ int lvk_hip_cas_const(float sharpness, float* peak)
 int lvk_hip_cas(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, int format, void* d_dst, int dst_step, float sharpness)
 {
     LVK_HIP_ENTRY(ctx);
-    int ch = 0;
-    if (!cas_format_channels(format, &ch)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_cas: packed BGR / RGB / YUV / BGRA / RGBA frames only");
+    const int ch = lvk_format_channels(format);
+    if (ch != 3 && ch != 4) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_cas: packed BGR / RGB / YUV / BGRA / RGBA frames only");
     if (!(sharpness >= 0.0f && sharpness <= 1.0f)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_cas: sharpness must lie in [0, 1] (CASFilter.cpp)");
     LVK_HIP_REQUIRE(ctx, d_src && d_dst && rows > 0 && cols > 0);
     const long long row_bytes = (long long)cols * ch;
     LVK_HIP_REQUIRE(ctx, (long long)src_step >= row_bytes && (long long)dst_step >= row_bytes);
     // CAS reads its neighbours: a destination that overlaps the source (in place included) would race
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((long long)(rows - 1) * src_step + row_bytes);
-    const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uintptr_t)((long long)(rows - 1) * dst_step + row_bytes);
-    if (s0 < t1 && t0 < s1) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_cas: the source and destination overlap");
+    if (lvk_pitched_overlap(d_src, src_step, rows, row_bytes, d_dst, dst_step, rows, row_bytes)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_cas: the source and destination overlap");
     float peak = 0.0f;
     lvk_hip_cas_const(sharpness, &peak);
 

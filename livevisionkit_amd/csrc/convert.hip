@@ -227,17 +227,6 @@ hipError_t launch(hipStream_t stream, const uint8_t* src, long long src_step, ui
     return hipGetLastError();
 }
 
-int format_channels(int format)
-{
-    switch (format)
-    {
-    case LVK_FORMAT_BGR: case LVK_FORMAT_RGB: case LVK_FORMAT_YUV: return 3;
-    case LVK_FORMAT_BGRA: case LVK_FORMAT_RGBA: return 4;
-    case LVK_FORMAT_GRAY: return 1;
-    default: return 0;
-    }
-}
-
 // VideoFrame::reformatTo's dispatch (VideoFrame.cpp:186-301); src != dst
 hipError_t dispatch(hipStream_t st, int from, int to, const uint8_t* s, long long ss, uint8_t* d, long long ds, int rows, int cols)
 {
@@ -302,13 +291,11 @@ int lvk_hip_reformat(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows
                      int dst_format)
 {
     LVK_HIP_ENTRY(ctx);
-    const int sc = format_channels(src_format), dc = format_channels(dst_format);
+    const int sc = lvk_format_channels(src_format), dc = lvk_format_channels(dst_format);
     if (!sc || !dc) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_reformat: unknown format (LVK_FORMAT_BGR .. LVK_FORMAT_GRAY)");
     LVK_HIP_REQUIRE(ctx, d_src && d_dst && rows > 0 && cols > 0);
     LVK_HIP_REQUIRE(ctx, (long long)src_step >= (long long)cols * sc && (long long)dst_step >= (long long)cols * dc);
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((long long)(rows - 1) * src_step + (long long)cols * sc);
-    const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uintptr_t)((long long)(rows - 1) * dst_step + (long long)cols * dc);
-    if (s0 < t1 && t0 < s1) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_reformat: the source and destination overlap");
+    if (lvk_pitched_overlap(d_src, src_step, rows, (long long)cols * sc, d_dst, dst_step, rows, (long long)cols * dc)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_reformat: the source and destination overlap");
     if (src_format == dst_format)
     {
         LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(d_dst, (size_t)dst_step, d_src, (size_t)src_step, (size_t)cols * sc, (size_t)rows,

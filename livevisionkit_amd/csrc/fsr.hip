@@ -246,16 +246,6 @@ void k_fsr_easu(EasuArgs a)
     }
 }
 
-bool fsr_format_channels(int format, int* channels)
-{
-    switch (format)
-    {
-    case LVK_FORMAT_BGR: case LVK_FORMAT_RGB: case LVK_FORMAT_YUV: *channels = 3; return true;
-    case LVK_FORMAT_BGRA: case LVK_FORMAT_RGBA: *channels = 4; return true;
-    default: return false;
-    }
-}
-
 // The largest fp span (last - first + 1) of any kTile-sized run of outputs 0 .. n - 1, with the kernel's float32 arithmetic.
 int max_fp_span(int n, int tile, float scale, float bias)
 {
@@ -332,17 +322,15 @@ int lvk_hip_fsr_easu(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows
                      int dst_step, int out_rows, int out_cols)
 {
     LVK_HIP_ENTRY(ctx);
-    int ch = 0;
-    if (!fsr_format_channels(format, &ch)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: packed BGR / RGB / YUV / BGRA / RGBA frames only");
+    const int ch = lvk_format_channels(format);
+    if (ch != 3 && ch != 4) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: packed BGR / RGB / YUV / BGRA / RGBA frames only");
     LVK_HIP_REQUIRE(ctx, d_src && d_dst && region_xywh && rows > 0 && cols > 0 && out_rows > 0 && out_cols > 0);
     const int rx = region_xywh[0], ry = region_xywh[1], rw = region_xywh[2], rh = region_xywh[3];
     if (!(rx >= 0 && ry >= 0 && rw > 0 && rh > 0 && (long long)rx + rw <= cols && (long long)ry + rh <= rows))
         return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: the region must be a non-empty rectangle inside the frame");
     const long long src_row = (long long)cols * ch, dst_row = (long long)out_cols * ch;
     LVK_HIP_REQUIRE(ctx, (long long)src_step >= src_row && (long long)dst_step >= dst_row);
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((long long)(rows - 1) * src_step + src_row);
-    const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uintptr_t)((long long)(out_rows - 1) * dst_step + dst_row);
-    if (s0 < t1 && t0 < s1) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: the source and destination overlap");
+    if (lvk_pitched_overlap(d_src, src_step, rows, src_row, d_dst, dst_step, out_rows, dst_row)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: the source and destination overlap");
 
     float con[16];
     lvk_hip_fsr_easu_const(rw, rh, cols, rows, out_cols, out_rows, con);

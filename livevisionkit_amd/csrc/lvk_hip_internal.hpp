@@ -174,6 +174,27 @@ struct LvkTimelineScope
 #define LVK_HIP_REQUIRE(ctx, cond)                                                                    \
     do { if (!(cond)) return (ctx)->fail(LVK_HIP_ERR_ARG, "pre-condition failed: " #cond); } while (0)
 
+// The packed channel count of an LVK_FORMAT_*: 3 (BGR / RGB / YUV), 4 (BGRA / RGBA), 1 (GRAY); 0 for an unknown format
+inline int lvk_format_channels(int format)
+{
+    switch (format)
+    {
+    case LVK_FORMAT_BGR: case LVK_FORMAT_RGB: case LVK_FORMAT_YUV: return 3;
+    case LVK_FORMAT_BGRA: case LVK_FORMAT_RGBA: return 4;
+    case LVK_FORMAT_GRAY: return 1;
+    default: return 0;
+    }
+}
+
+// Whether two pitched byte ranges (`rows` rows of `row_bytes` bytes, `step` bytes apart) share a byte: an out-of-place kernel that reads
+// neighbours must not write over its source (in place included)
+inline bool lvk_pitched_overlap(const void* a, int a_step, int a_rows, long long a_row_bytes, const void* b, int b_step, int b_rows, long long b_row_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)((long long)(a_rows - 1) * a_step + a_row_bytes);
+    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)((long long)(b_rows - 1) * b_step + b_row_bytes);
+    return a0 < b1 && b0 < a1;
+}
+
 // Copies `bytes` (<= kStageBytes) of host data into a device staging slot, asynchronously on the
 // context's stream, and returns the device address.  The slot is recycled after kStageSlots uses.
 // With `slot` != nullptr the slot is NOT marked consumed by the copy: the caller launches the kernel that reads it and then calls

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _native
-from .stabilization import FORMAT_YUV
+from .stabilization import FORMAT_YUV, frame_args
 
 _c = ctypes
 
@@ -23,9 +23,7 @@ class DeblockingFilterSettings(_c.Structure):
 
 
 def _frame_args(frame):
-    if frame.dim() != 3 or frame.shape[2] != 3 or frame.stride(2) != 1 or frame.stride(1) != 3 or frame.dtype.itemsize != 1:
-        raise ValueError("a packed 8UC3 frame [rows, cols, 3] with contiguous rows is required")
-    return frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1]
+    return (*frame_args(frame, 3, "8UC3"), frame.shape[0], frame.shape[1])
 
 
 class DeblockingFilter:

@@ -6,10 +6,9 @@ import ctypes
 import math
 
 from . import _native
-from .stabilization import FORMAT_BGR
+from .stabilization import CHANNELS, FORMAT_BGR, frame_args, out_frame
 
 _c = ctypes
-_CHANNELS = {0: 3, 2: 3, 4: 3, 1: 4, 3: 4}      # LVK_FORMAT_BGR, _RGB, _YUV; _BGRA, _RGBA
 MAX_CROP = 4096
 
 
@@ -31,13 +30,6 @@ def fsr_geometry(rows, cols, output_size=None, multiplier=1.0, maintain_aspect_r
     if rc != 0:
         raise ValueError("invalid FSR geometry arguments")
     return tuple(region), tuple(size), bool(skip.value)
-
-
-def _frame_args(frame, channels):
-    if (frame.dim() != 3 or frame.shape[2] != channels or frame.stride(2) != 1 or frame.stride(1) != channels
-            or frame.dtype.itemsize != 1):
-        raise ValueError("a packed uint8 frame [rows, cols, %d] with contiguous rows is required" % channels)
-    return frame.data_ptr(), frame.stride(0)
 
 
 class FSRFilter:
@@ -70,11 +62,10 @@ class FSRFilter:
     def apply(self, frame, fmt=FORMAT_BGR, out=None):
         """Scales `frame` into `out` (a new tensor of the output size when None; it must not overlap `frame`) and returns it.  When the
         geometry skips, `frame` itself is returned (or copied into `out`)."""
-        import torch
-        if fmt not in _CHANNELS:
+        ch = CHANNELS.get(fmt)
+        if ch not in (3, 4):
             raise ValueError("FSR takes BGR / RGB / YUV and BGRA / RGBA frames")
-        ch = _CHANNELS[fmt]
-        src, src_step = _frame_args(frame, ch)
+        src, src_step = frame_args(frame, ch)
         rows, cols = frame.shape[0], frame.shape[1]
         region, (oh, ow), skip = self.geometry(rows, cols)
         if skip:
@@ -84,11 +75,8 @@ class FSRFilter:
                 raise ValueError("out must have the shape of the frame")
             out.copy_(frame)
             return out
-        if out is None:
-            out = torch.empty((oh, ow, ch), dtype=torch.uint8, device=frame.device)
-        if tuple(out.shape) != (oh, ow, ch):
-            raise ValueError("out must have the output shape %r" % ((oh, ow, ch),))
-        dst, dst_step = _frame_args(out, ch)
+        out = out_frame(out, frame, (oh, ow, ch), "out must have the output shape %r" % ((oh, ow, ch),))
+        dst, dst_step = frame_args(out, ch)
         self.ctx._check(self.lib.lvk_hip_fsr_easu(self.ctx.handle, src, src_step, rows, cols, int(fmt), (_c.c_int * 4)(*region), dst, dst_step,
                                                   oh, ow))
         return out

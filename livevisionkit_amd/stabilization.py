@@ -13,6 +13,26 @@ from .context import Context
 _c = ctypes
 
 FORMAT_BGR, FORMAT_BGRA, FORMAT_RGB, FORMAT_RGBA, FORMAT_YUV, FORMAT_GRAY = range(6)
+CHANNELS = {FORMAT_BGR: 3, FORMAT_BGRA: 4, FORMAT_RGB: 3, FORMAT_RGBA: 4, FORMAT_YUV: 3, FORMAT_GRAY: 1}
+
+
+def frame_args(frame, channels, kind="uint8"):
+    """(data pointer, row pitch) of a packed frame [rows, cols, channels] with contiguous rows (any row pitch)."""
+    if (frame.dim() != 3 or frame.shape[2] != channels or frame.stride(2) != 1 or frame.stride(1) != channels
+            or frame.dtype.itemsize != 1):
+        raise ValueError("a packed %s frame [rows, cols, %d] with contiguous rows is required" % (kind, channels))
+    return frame.data_ptr(), frame.stride(0)
+
+
+def out_frame(out, frame, shape, message):
+    """The destination of an out-of-place filter: a new uint8 tensor of `shape` on `frame`'s device when `out` is None, else `out`
+    (ValueError(message) unless it has `shape`)."""
+    if out is None:
+        import torch
+        return torch.empty(shape, dtype=torch.uint8, device=frame.device)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(message)
+    return out
 
 
 class StabilizationFilterSettings(_c.Structure):

@@ -6,44 +6,23 @@
 //   CompositeFilter{DeblockingFilter, CASFilter} with default deblocking settings: deblock, then sharpen.
 // cas_facade --stream <obs format> <rows> <cols> <n frames> <sharpness> <planes.bin> <out.bin>
 //   upload_obs_frame -> CASFilter::apply(std::move(frame), frame) -> download_ocl_frame; out.bin = the frames' tight planes.
+// cas_facade cross <sharpness>
+//   two CASFilters on contexts A and B, each fed frames of the other's context from its own thread; the outputs must equal single-threaded runs.
 // cas_facade configure
 //   configure({1.5}) and CASFilter({-0.25}) must be refused (the assert handler throws); needs no device.
 #include <lvk/LiveVisionKit.hpp>
 #include <lvk/FrameIngest.hpp>
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
-struct fake_obs_source_frame            // the members of libobs' obs_source_frame the plugin's FrameIngest touches
-{
-    uint8_t* data[8] = {};
-    uint32_t linesize[8] = {};
-    uint32_t width = 0, height = 0;
-    uint64_t timestamp = 0;
-    int format = 0;
-};
-
-static bool read_file(const char* path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    const bool ok = std::fread(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
-
-static bool write_file(const char* path, const std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path, "wb");
-    if (!f) return false;
-    const bool ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
+#include "facade_util.hpp"
 
 static int run_apply(char** argv, bool chain)
 {
@@ -108,6 +87,57 @@ static int run_stream(char** argv)
     return 0;
 }
 
+// The cross-context fences take both contexts' locks (Context::wait_for).  Taken while a filter still holds its own lock, two filters on
+// contexts A and B, fed from two threads with frames of each other's context, each keep their own mutex while waiting for the other's.  A
+// filter adopts the context of its first frame, so each is primed with a frame of its own.  A watchdog turns a hang into a failure.
+static int run_cross(char** argv)
+{
+    const int rows = 36, cols = 64, n = 2000, distinct = 16;      // small frames, many applies: the window is microseconds wide
+    const lvk::CASFilterSettings s{(float)std::atof(argv[2])};
+    std::vector<uint8_t> pixels[2][distinct];
+    for (int t = 0; t < 2; t++)
+        for (int i = 0; i < distinct; i++)
+        {
+            pixels[t][i].resize((size_t)rows * cols * 3);
+            for (size_t k = 0; k < pixels[t][i].size(); k++) pixels[t][i][k] = (uint8_t)((k * (5 + 2 * t) + 31 * i) % 251);
+        }
+    using Ctx = std::shared_ptr<lvk::hip::Context>;
+    using Outputs = std::vector<std::vector<uint8_t>>;
+    // thread t: a filter primed on filter_ctx, then fed frames uploaded on frames_ctx; one output in a hundred is kept (a download synchronises)
+    auto feed = [&](int t, const Ctx& frames_ctx, const Ctx& filter_ctx, Outputs& outs) {
+        lvk::CASFilter filter(s);
+        lvk::Frame frame;
+        frame.upload(pixels[t][0].data(), rows, cols, lvk::VideoFrame::BGR, 0, filter_ctx);
+        filter.apply(std::move(frame), frame);
+        for (int i = 0; i < n; i++)
+        {
+            frame.upload(pixels[t][i % distinct].data(), rows, cols, lvk::VideoFrame::BGR, i, frames_ctx);
+            filter.apply(std::move(frame), frame);
+            if (i % 100 != 99) continue;
+            outs.emplace_back(pixels[t][0].size());
+            frame.download(outs.back().data());
+        }
+    };
+    Outputs want[2];
+    for (int t = 0; t < 2; t++) { auto c = std::make_shared<lvk::hip::Context>(); feed(t, c, c, want[t]); }
+    if (want[0].size() != (size_t)n / 100 || want[0][5] == want[1][5]) { std::printf("cross: reference runs implausible\n"); return 1; }
+    for (int round = 0; round < 3; round++)
+    {
+        auto A = std::make_shared<lvk::hip::Context>(), B = std::make_shared<lvk::hip::Context>();
+        Outputs got[2];
+        std::atomic<int> done{0};
+        std::thread t0([&] { feed(0, B, A, got[0]); done++; });          // filter on A, frames on B
+        std::thread t1([&] { feed(1, A, B, got[1]); done++; });          // filter on B, frames on A
+        for (int ms = 0; ms < 60000 && done.load() < 2; ms += 5) std::this_thread::sleep_for(std::chrono::milliseconds(5));
+        if (done.load() < 2) { std::printf("cross: DEADLOCK (two CASFilters on two contexts feeding each other, round %d)\n", round); std::fflush(stdout); std::_Exit(1); }
+        t0.join(); t1.join();
+        for (int t = 0; t < 2; t++)
+            if (got[t] != want[t]) { std::printf("cross: thread %d's outputs differ from its single-threaded run (round %d)\n", t, round); return 1; }
+    }
+    std::printf("cross ok: 2 CASFilters on 2 contexts feeding each other from 2 threads: no deadlock, bytes equal\n");
+    return 0;
+}
+
 static int run_configure()
 {
     lvk::context::assert_handler = [](std::string, std::string, std::string assertion) { throw std::runtime_error(assertion); };
@@ -128,6 +158,7 @@ int main(int argc, char** argv)
     if (argc == 8 && std::string(argv[1]) == "apply") return run_apply(argv, false);
     if (argc == 8 && std::string(argv[1]) == "chain") return run_apply(argv, true);
     if (argc == 9 && std::string(argv[1]) == "--stream") return run_stream(argv);
+    if (argc == 3 && std::string(argv[1]) == "cross") return run_cross(argv);
     if (argc == 2 && std::string(argv[1]) == "configure") return run_configure();
     std::fprintf(stderr, "usage: see the head of cas_facade.cpp\n");
     return 2;

@@ -26,34 +26,9 @@
 #include <string>
 #include <vector>
 
-struct fake_obs_source_frame            // the members of libobs' obs_source_frame the plugin's FrameIngest touches
-{
-    uint8_t* data[8] = {};
-    uint32_t linesize[8] = {};
-    uint32_t width = 0, height = 0;
-    uint64_t timestamp = 0;
-    int format = 0;
-};
+#include "facade_util.hpp"
 
 using Format = lvk::VideoFrame::Format;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    const bool ok = std::fread(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
-
-static bool write_file(const std::string& path, const std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
 
 static std::vector<uint8_t> download(const lvk::VideoFrame& f)
 {

@@ -16,14 +16,7 @@
 #include <string>
 #include <vector>
 
-struct fake_obs_source_frame            // the members of libobs' obs_source_frame the plugin's FrameIngest touches
-{
-    uint8_t* data[8] = {};
-    uint32_t linesize[8] = {};
-    uint32_t width = 0, height = 0;
-    uint64_t timestamp = 0;
-    int format = 0;
-};
+#include "facade_util.hpp"
 
 static int run_apply(char** argv)
 {
@@ -32,9 +25,7 @@ static int run_apply(char** argv)
     s.detection_levels = (uint32_t)std::atoi(argv[5]); s.block_size = (uint32_t)std::atoi(argv[6]);
     s.filter_size = (uint32_t)std::atoi(argv[7]); s.filter_scaling = (float)std::atof(argv[8]);
     std::vector<uint8_t> host((size_t)rows * cols * 3);
-    FILE* f = std::fopen(argv[9], "rb");
-    if (!f || std::fread(host.data(), 1, host.size(), f) != host.size()) return 2;
-    std::fclose(f);
+    if (!read_file(argv[9], host)) return 2;
     const std::string prefix = argv[10];
 
     lvk::DeblockingFilter filter(s);
@@ -43,10 +34,10 @@ static int run_apply(char** argv)
     filter.apply(frame, frame, true);
     if (frame.timestamp != 7 || frame.rows != rows || frame.cols != cols) return 1;
     frame.download(host.data());
-    f = std::fopen((prefix + ".apply").c_str(), "wb"); std::fwrite(host.data(), 1, host.size(), f); std::fclose(f);
+    if (!write_file(prefix + ".apply", host)) return 2;
     filter.draw_influence(frame);
     frame.download(host.data());
-    f = std::fopen((prefix + ".influence").c_str(), "wb"); std::fwrite(host.data(), 1, host.size(), f); std::fclose(f);
+    if (!write_file(prefix + ".influence", host)) return 2;
     const cv::Rect r = filter.filter_region();
     std::printf("apply ok: region %d %d %d %d\n", r.x, r.y, r.width, r.height);
     return 0;
@@ -59,9 +50,7 @@ static int run_stream(char** argv)
     if (fmt != 1) return 2;                                  // I420
     const size_t ybytes = (size_t)rows * cols, cbytes = (size_t)(rows / 2) * (cols / 2), frame_bytes = ybytes + 2 * cbytes;
     std::vector<uint8_t> clip(frame_bytes * n), back(frame_bytes);
-    FILE* f = std::fopen(argv[8], "rb");
-    if (!f || std::fread(clip.data(), 1, clip.size(), f) != clip.size()) return 2;
-    std::fclose(f);
+    if (!read_file(argv[8], clip)) return 2;
     FILE* out = std::fopen(argv[9], "wb");
     if (!out) return 2;
     auto ingest = lvk::FrameIngest::Select(fmt);

@@ -10,14 +10,7 @@
 #include <cstring>
 #include <vector>
 
-struct fake_obs_source_frame            // the members of libobs' obs_source_frame the plugin's FrameIngest touches
-{
-    uint8_t* data[8] = {};
-    uint32_t linesize[8] = {};
-    uint32_t width = 0, height = 0;
-    uint64_t timestamp = 0;
-    int format = 0;
-};
+#include "facade_util.hpp"
 
 static int plane_table(int fmt, int rows, int cols, int prow[3], int pbytes[3], int pwritten[3])
 {
@@ -47,9 +40,7 @@ static int run_stream(int argc, char** argv)
     size_t frame_bytes = 0;
     for (int i = 0; i < np; i++) frame_bytes += (size_t)prow[i] * pbytes[i];
     std::vector<uint8_t> clip(frame_bytes * n), back(frame_bytes);
-    FILE* f = std::fopen(argv[7], "rb");
-    if (!f || std::fread(clip.data(), 1, clip.size(), f) != clip.size()) return 2;
-    std::fclose(f);
+    if (!read_file(argv[7], clip)) return 2;
     FILE* out = std::fopen(argv[8], "wb");
     if (!out) return 2;
     auto ingest = lvk::FrameIngest::Select(fmt);
@@ -127,7 +118,7 @@ int main(int argc, char** argv)
     std::vector<uint8_t> host((size_t)rows * cols * 3);
     frame.download(host.data());
     std::string prefix = argv[6];
-    f = std::fopen((prefix + ".frame").c_str(), "wb"); std::fwrite(host.data(), 1, host.size(), f); std::fclose(f);
+    if (!write_file(prefix + ".frame", host)) return 2;
 
     // and back, into planes with the same pitch that hold 0x5A: bytes the reference does not write keep it
     fake_obs_source_frame out;

@@ -19,32 +19,7 @@
 #include <string>
 #include <vector>
 
-struct fake_obs_source_frame            // the members of libobs' obs_source_frame the plugin's FrameIngest touches
-{
-    uint8_t* data[8] = {};
-    uint32_t linesize[8] = {};
-    uint32_t width = 0, height = 0;
-    uint64_t timestamp = 0;
-    int format = 0;
-};
-
-static bool read_file(const char* path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    const bool ok = std::fread(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
-
-static bool write_file(const char* path, const std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path, "wb");
-    if (!f) return false;
-    const bool ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
+#include "facade_util.hpp"
 
 static int channels_of(int fmt) { return fmt == 1 || fmt == 3 ? 4 : 3; }
 

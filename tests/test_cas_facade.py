@@ -8,19 +8,14 @@ import numpy as np
 import pytest
 
 from tests import np_cas as nc
+from tests.facade import build_facade
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "cas_facade.cpp")
 
 
 def _build(tmp_path):
-    import torch
-    tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = str(tmp_path / "cas_facade")
-    subprocess.check_call(["g++", "-std=c++20", "-Wall", "-O1", "-I" + os.path.join(ROOT, "include"), "-o", exe, SRC,
-                           "-L" + os.path.join(ROOT, "livevisionkit_amd"), "-llvk_hip", "-L" + tlib, "-l:libamdhip64.so",
-                           "-Wl,-rpath," + os.path.join(ROOT, "livevisionkit_amd"), "-Wl,-rpath," + tlib])
-    return exe
+    return build_facade(tmp_path, SRC, ["-pthread"])         # (the cross mode runs two threads)
 
 
 def test_facade_cas_filter_compiles(tmp_path):
@@ -61,6 +56,14 @@ def test_facade_deblock_then_sharpen_chain(tmp_path, rows, cols, fmt, sharpness)
     deblocked, _ = nd.deblock(img, fmt)
     assert not np.array_equal(deblocked, img)
     assert np.array_equal(np.fromfile(tmp_path / "out.bin", np.uint8).reshape(rows, cols, 3), nc.cas(deblocked, sharpness))
+
+
+@pytest.mark.gpu
+def test_facade_two_contexts_feeding_each_other_from_two_threads(tmp_path):
+    # the cross-context fences take both contexts' locks: taken under a filter's own lock they deadlock two filters that feed each other
+    exe = _build(tmp_path)
+    r = subprocess.run([exe, "cross", "0.8"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "cross ok" in r.stdout, (r.stdout, r.stderr)
 
 
 @pytest.mark.gpu

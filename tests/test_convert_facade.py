@@ -10,19 +10,10 @@ import numpy as np
 import pytest
 
 from tests import np_convert as nc
+from tests.facade import build_facade
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "convert_facade.cpp")
-
-
-def _build(tmp_path):
-    import torch
-    tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = str(tmp_path / "convert_facade")
-    subprocess.check_call(["g++", "-std=c++20", "-Wall", "-O1", "-I" + os.path.join(ROOT, "include"), "-o", exe, SRC,
-                           "-L" + os.path.join(ROOT, "livevisionkit_amd"), "-llvk_hip", "-L" + tlib, "-l:libamdhip64.so",
-                           "-Wl,-rpath," + os.path.join(ROOT, "livevisionkit_amd"), "-Wl,-rpath," + tlib])
-    return exe
 
 
 def _inputs(tmp_path, rows, cols, seed):
@@ -39,12 +30,12 @@ def _read(path, rows, cols, fmt):
 
 
 def test_facade_conversion_filter_compiles(tmp_path):
-    _build(tmp_path)
+    build_facade(tmp_path, SRC)
 
 
 def test_facade_configure_refuses_unsupported_codes(tmp_path):
     # unsupported codes and output channels reach the assert handler; a refused configure keeps the settings (no device is touched)
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     r = subprocess.run([exe, "configure"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "configure ok: 6 refused, alias Conversion Filter" in r.stdout, (r.stdout, r.stderr)
 
@@ -52,7 +43,7 @@ def test_facade_configure_refuses_unsupported_codes(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("rows,cols", [(1, 1), (17, 65), (270, 480)])
 def test_facade_frames_of_one_three_and_four_channels(tmp_path, rows, cols):
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     r = subprocess.run([exe, "frames", str(rows), str(cols)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "frames ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
@@ -60,7 +51,7 @@ def test_facade_frames_of_one_three_and_four_channels(tmp_path, rows, cols):
 @pytest.mark.gpu
 @pytest.mark.parametrize("rows,cols", [(3, 5), (31, 67), (1080, 1920)])
 def test_facade_reformat_reformat_to_and_view_as_format(tmp_path, rows, cols):
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     imgs = _inputs(tmp_path, rows, cols, seed=rows + cols)
     r = subprocess.run([exe, "reformat", str(rows), str(cols), str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "reformat ok: 36 pairs" in r.stdout, (r.returncode, r.stdout, r.stderr)
@@ -75,7 +66,7 @@ def test_facade_reformat_reformat_to_and_view_as_format(tmp_path, rows, cols):
 @pytest.mark.gpu
 def test_facade_conversion_filter_every_code(tmp_path):
     rows, cols = 45, 83
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     imgs = _inputs(tmp_path, rows, cols, seed=9)
     r = subprocess.run([exe, "filter", str(rows), str(cols), str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "filter ok:" in r.stdout and "Conversion Filter" in r.stdout, (r.returncode, r.stdout, r.stderr)
@@ -94,7 +85,7 @@ def test_facade_conversion_filter_every_code(tmp_path):
 def test_facade_yuv_to_bgr_sharpen_and_back_chain(tmp_path, rows, cols, sharpness):
     from tests import np_cas
     from tests.test_cas_gpu import content
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     img = content(rows, cols, 3, seed=rows + 11)
     img.tofile(tmp_path / "frame.bin")
     r = subprocess.run([exe, "chain", str(rows), str(cols), repr(sharpness), str(tmp_path / "frame.bin"), str(tmp_path / "out.bin")],
@@ -107,7 +98,7 @@ def test_facade_yuv_to_bgr_sharpen_and_back_chain(tmp_path, rows, cols, sharpnes
 @pytest.mark.gpu
 def test_facade_obs_i420_export_as_rgba(tmp_path, oracle):
     from tests import synth
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     rows, cols, n = 270, 480, 3
     clip, _ = synth.make_clip(rows, cols, n, seed=71, jitter=1.0)
     want = []

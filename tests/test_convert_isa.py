@@ -1,32 +1,15 @@
 """Register / scratch budget and memory instructions of the format conversion kernels (csrc/convert.hip), read from the gfx950 assembly hipcc
 emits with the Makefile's flags (no GPU needed), as tests/test_cas_isa.py does for CAS: no scratch, at most 64 VGPRs, and the interior-path
 kernels move their bytes as whole dwords (dwordx4 / dwordx3), never a byte at a time, with v_perm_b32 for the byte moves."""
-import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livevisionkit_amd", "csrc")
+from tests.isa import assemble
+
 MAP_OPS = {0, 1, 2, 3, 4}          # OP_KEEP, OP_SWAP, OP_REP, OP_Y, OP_G2YUV: byte moves only
 
 
-def _makefile_flags():
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^HIPFLAGS = (.*)$", text, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    return [f.replace("-I../../include", "-I" + os.path.join(ROOT, "include")).replace("-I.", "-I" + CSRC) if f.startswith("-I") else f
-            for f in flags]
-
-
 def test_convert_kernels_budget_and_instructions():
-    out = subprocess.run(["/opt/rocm/bin/hipcc", *_makefile_flags(), "-S", "--cuda-device-only", "-o", "-", os.path.join(CSRC, "convert.hip")],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    code = out.stdout
-    kernels = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", code, re.S):
-        body = m.group(2)
-        kernels[m.group(1)] = (int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)),
-                               int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)))
+    code, kernels = assemble("convert")
     # 22 (source channels, destination channels, operation) instantiations, each with an interior and a general kernel
     assert len(kernels) == 44 and all("k_convert_" in k for k in kernels), sorted(kernels)
     for name, (scratch, vgprs) in kernels.items():

@@ -8,30 +8,21 @@ import numpy as np
 import pytest
 
 from tests import np_deblock as nd
+from tests.facade import build_facade
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "deblocking_facade.cpp")
 
 
-def _build(tmp_path):
-    import torch
-    tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = str(tmp_path / "deblocking_facade")
-    subprocess.check_call(["g++", "-std=c++20", "-Wall", "-O1", "-I" + os.path.join(ROOT, "include"), "-o", exe, SRC,
-                           "-L" + os.path.join(ROOT, "livevisionkit_amd"), "-llvk_hip", "-L" + tlib, "-l:libamdhip64.so",
-                           "-Wl,-rpath," + os.path.join(ROOT, "livevisionkit_amd"), "-Wl,-rpath," + tlib])
-    return exe
-
-
 def test_facade_deblocking_filter_compiles(tmp_path):
-    _build(tmp_path)
+    build_facade(tmp_path, SRC)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("rows,cols,fmt,levels,bs,k,s", [(270, 480, 4, 3, 16, 5, 4.0), (131, 67, 0, 5, 8, 7, 3.0), (1080, 1920, 2, 1, 16, 3, 2.0)])
 def test_facade_apply_and_draw_influence(tmp_path, rows, cols, fmt, levels, bs, k, s):
     from tests.test_deblock_gpu import blocky
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     img = blocky(rows, cols, seed=rows * 7 + k)
     img.tofile(tmp_path / "frame.bin")
     prefix = str(tmp_path / "out")
@@ -47,7 +38,7 @@ def test_facade_apply_and_draw_influence(tmp_path, rows, cols, fmt, levels, bs, 
 @pytest.mark.parametrize("with_stab", [0, 1])
 def test_facade_obs_path_and_composite_chain(tmp_path, oracle, with_stab):
     from tests import oracle_lib, synth
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     rows, cols, n, delay = 270, 480, 10, 3
     clip, _ = synth.make_clip(rows, cols, n, seed=61, jitter=1.0)
     ost = None

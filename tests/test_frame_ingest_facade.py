@@ -7,29 +7,21 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.facade import build_facade
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "frame_ingest_facade.cpp")
 FORMATS = {"I420": 1, "NV12": 2, "YVYU": 3, "YUY2": 4, "UYVY": 5, "RGBA": 6, "BGRA": 7, "BGRX": 8, "I444": 10, "BGR3": 11, "I422": 12, "I40A": 13,
            "I42A": 14, "YUVA": 15, "AYUV": 16}
 
 
-def _build(tmp_path):
-    import torch
-    tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = str(tmp_path / "frame_ingest_facade")
-    subprocess.check_call(["g++", "-std=c++20", "-Wall", "-O1", "-I" + os.path.join(ROOT, "include"), "-o", exe, SRC,
-                           "-L" + os.path.join(ROOT, "livevisionkit_amd"), "-llvk_hip", "-L" + tlib, "-l:libamdhip64.so",
-                           "-Wl,-rpath," + os.path.join(ROOT, "livevisionkit_amd"), "-Wl,-rpath," + tlib])
-    return exe
-
-
 def test_facade_frame_ingest_compiles(tmp_path):
-    _build(tmp_path)
+    build_facade(tmp_path, SRC)
 
 
 @pytest.mark.gpu
 def test_facade_frame_ingest_every_format(tmp_path, oracle):
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     for name, fmt in FORMATS.items():
         for (rows, cols), pad in (((36, 52), 0), ((270, 480), 12)):
             rng = np.random.default_rng(fmt * 1000 + rows)
@@ -58,7 +50,7 @@ def test_facade_ingest_filter_download_chain(tmp_path, oracle, name):
     """upload_obs_frame -> StabilizationFilter::apply(std::move(frame), frame) -> download_ocl_frame, the plugin's asynchronous path with the facade's
     classes (Interop/VisionFilter.cpp:151-253 around VSFilter.cpp:352-364), against the oracle's ingest -> filter -> egress."""
     from tests import oracle_lib, synth
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     rows, cols, n, delay = 270, 480, 12, 3
     clip, _ = synth.make_clip(rows, cols, n, seed=53, jitter=1.0)
     fmt = FORMATS[name]

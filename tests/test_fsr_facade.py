@@ -10,28 +10,19 @@ import pytest
 
 from tests import np_cas as nc
 from tests import np_fsr as nf
+from tests.facade import build_facade
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "fsr_facade.cpp")
 
 
-def _build(tmp_path):
-    import torch
-    tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = str(tmp_path / "fsr_facade")
-    subprocess.check_call(["g++", "-std=c++20", "-Wall", "-O1", "-I" + os.path.join(ROOT, "include"), "-o", exe, SRC,
-                           "-L" + os.path.join(ROOT, "livevisionkit_amd"), "-llvk_hip", "-L" + tlib, "-l:libamdhip64.so",
-                           "-Wl,-rpath," + os.path.join(ROOT, "livevisionkit_amd"), "-Wl,-rpath," + tlib])
-    return exe
-
-
 def test_facade_fsr_filter_compiles(tmp_path):
-    _build(tmp_path)
+    build_facade(tmp_path, SRC)
 
 
 def test_facade_configure_refuses_bad_settings(tmp_path):
     # negative or > 4096 crops, a multiplier <= 0 or NaN, a negative size reach the assert handler; a refused configure keeps the settings
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     r = subprocess.run([exe, "configure"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "configure ok: 7 refused, alias FSR Filter" in r.stdout, (r.stdout, r.stderr)
 
@@ -61,7 +52,7 @@ def _run(exe, tmp_path, mode, args):
 @pytest.mark.gpu
 @pytest.mark.parametrize("args", MODES)
 def test_facade_apply(tmp_path, args):
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     img, r = _run(exe, tmp_path, "apply", args)
     fmt, rows, cols, out_size, m, aspect, crop = args
     want = nf.fsr_filter(img, fmt, out_size, m, aspect, crop)
@@ -72,7 +63,7 @@ def test_facade_apply(tmp_path, args):
 @pytest.mark.gpu
 @pytest.mark.parametrize("args", [MODES[0], MODES[2], MODES[3]])
 def test_facade_scale_then_sharpen_chain(tmp_path, args):
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     img, r = _run(exe, tmp_path, "chain", args)
     fmt, rows, cols, out_size, m, aspect, crop = args
     want = nc.cas(nf.fsr_filter(img, fmt, out_size, m, aspect, crop), 0.8)
@@ -83,7 +74,7 @@ def test_facade_scale_then_sharpen_chain(tmp_path, args):
 @pytest.mark.gpu
 def test_facade_obs_i420_path(tmp_path, oracle):
     from tests import synth
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     rows, cols, n, m = 270, 480, 3, 2.0
     clip, _ = synth.make_clip(rows, cols, n, seed=71, jitter=1.0)
     want = []

@@ -5,35 +5,18 @@ Round 3 lost 2x on k_mesh_backsolve to an innocent-looking refactor (its LDS arr
 CPU: no kernel may use scratch, and the kernels whose occupancy the schedule depends on stay within their VGPR budgets (DESIGN.md
 sections 4-5: the remap's persistent grid needs <= 80 VGPRs to fit 4 blocks per CU next to the tracker; k_ransac_finalize runs 8 waves of
 <= 96 VGPRs so that two of them per SIMD fit next to the remap's 4 x 80)."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livevisionkit_amd", "csrc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-         "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
-MESH_FLAGS = ["-mllvm", "-amdgpu-load-store-vectorizer=0", "-Xclang", "-target-feature", "-Xclang", "-load-store-opt"]      # as csrc/Makefile
+from tests.isa import assemble
+
 VGPR_BUDGET = {r"k_fast_insert": 48, r"k_remap_\w+": 80, r"k_easu_scale": 80, r"k_ransac_finalize": 96, r"k_mesh_backsolve(?!_generic)": 168, r"k_pyrlk": 96, r"k_mesh_solve(?!_generic)": 256}
-
-
-def _kernels(unit):
-    out = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *(MESH_FLAGS if unit == "mesh" else []), "-S", "--cuda-device-only", "-o", "-",
-                          os.path.join(CSRC, unit + ".hip")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.stdout, re.S):
-        body = m.group(2)
-        res[m.group(1)] = (int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)),
-                           int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)))
-    return res
 
 
 @pytest.mark.parametrize("unit", ["remap", "mesh", "motion", "pyrlk", "fast", "imgproc", "ingest", "sharpen", "draw", "lens"])
 def test_no_scratch_and_vgpr_budgets(unit):
-    kernels = _kernels(unit)
+    _, kernels = assemble(unit)
     assert kernels, unit
     for name, (scratch, vgprs) in kernels.items():
         assert scratch == 0, f"{name}: {scratch} bytes of scratch"
@@ -51,12 +34,10 @@ def test_remap_instruction_ceiling():
     kernel (was 2 241), no v_mad_u64_u32 anywhere in them and a handful of v_lshl_add_u64 per THREAD (ragged-edge stores) instead of 6-7
     per pixel -- and made `coord - floor(coord)` one v_fract_f32 (exact for every coordinate that reaches the EASU path): 2 058.  This test keeps a refactor from quietly adding to it, and holds the round-4 savings in place: EASU's saturate as the
     `clamp` modifier of the multiply that feeds it and the final clamp between the centre taps' minimum and maximum as one v_med3_f32."""
-    out = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-S", "--cuda-device-only", "-o", "-", os.path.join(CSRC, "remap.hip")],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
+    code, _ = assemble("remap")
 
     def bodies_of(kernel):
-        return {m.group(1): m.group(2) for m in re.finditer(r"^(\S*" + kernel + r"I\S*):[^\n]*\n(.*?)\.Lfunc_end", out.stdout, re.S | re.M)}
+        return {m.group(1): m.group(2) for m in re.finditer(r"^(\S*" + kernel + r"I\S*):[^\n]*\n(.*?)\.Lfunc_end", code, re.S | re.M)}
 
     def valu_of(body):
         ops = [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith((";", ".", "//")) and not ln.strip().endswith(":")]

@@ -11,20 +11,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.facade import build_facade
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "warp_mesh_facade.cpp")
 f32 = np.float32
 KH = np.array([1.01, 0.012, 3.1, -0.011, 0.995, -2.2, 2e-5, -1e-5, 1.0])
-
-
-def _build(tmp_path):
-    import torch
-    tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = str(tmp_path / "warp_mesh_facade")
-    subprocess.check_call(["g++", "-std=c++20", "-Wall", "-O1", "-I" + os.path.join(ROOT, "include"), "-o", exe, SRC,
-                           "-L" + os.path.join(ROOT, "livevisionkit_amd"), "-llvk_hip", "-L" + tlib, "-l:libamdhip64.so",
-                           "-Wl,-rpath," + os.path.join(ROOT, "livevisionkit_amd"), "-Wl,-rpath," + tlib])
-    return exe
 
 
 # ---- numpy restatement (binary32 unless stated; one rounding per operation, no contraction) -------------------------------------------------------
@@ -93,7 +85,7 @@ def full_size_mesh(rows, cols):
 
 
 def test_host_arithmetic_matches_a_numpy_restatement(tmp_path):
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     out = subprocess.check_output([exe]).decode()
     assert "host part done" in out
     got = {}
@@ -150,7 +142,7 @@ def test_apply_and_remap_match_the_oracle(tmp_path, oracle):
     rows, cols = 270, 480
     src = synth.textured_frame(rows, cols, seed=11)
     (tmp_path / "in.bin").write_bytes(struct.pack("<ii", rows, cols) + src.tobytes())
-    exe = _build(tmp_path)
+    exe = build_facade(tmp_path, SRC)
     out = subprocess.check_output([exe, "--gpu", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], timeout=300).decode()
     assert "gpu part done: 7 frames" in out, out
     got = np.frombuffer((tmp_path / "out.bin").read_bytes(), np.uint8).reshape(7, rows, cols, 3)
