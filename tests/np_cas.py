@@ -32,9 +32,13 @@ def _as_u32(v):
     return np.asarray(v, dtype=f32).view(u32)
 
 
+LO_RCP_BITS = 0x7ef07ebb
+MED_RCP_BITS = 0x7ef19fff
+
+
 def lo_rcp(v):
     """APrxLoRcpF1: as_float(0x7ef07ebb - as_uint(v))."""
-    return _as_f32(u32(0x7ef07ebb) - _as_u32(v))
+    return _as_f32(u32(LO_RCP_BITS) - _as_u32(v))
 
 
 def lo_sqrt(v):
@@ -45,7 +49,7 @@ def lo_sqrt(v):
 def med_rcp(v):
     """APrxMedRcpF1: r = as_float(0x7ef19fff - as_uint(v)); r * ((-r) * v + 2), each operation rounded on its own."""
     v = np.asarray(v, dtype=f32)
-    r = _as_f32(u32(0x7ef19fff) - _as_u32(v))
+    r = _as_f32(u32(MED_RCP_BITS) - _as_u32(v))
     return r * ((-r) * v + f32(2))
 
 
@@ -82,17 +86,30 @@ def _window(x):
     return [p[dy:dy + rows, dx:dx + cols] for dy in range(3) for dx in range(3)]
 
 
+def soft_min(a, b, c, d, e, f, g, h, i):
+    """The plus-shaped minimum added to the minimum over the whole window (CAS_BETTER_DIAGONALS): twice the soft minimum."""
+    mn = np.minimum(np.minimum(np.minimum(d, e), f), np.minimum(b, h))
+    return mn + np.minimum(np.minimum(mn, a), np.minimum(np.minimum(c, g), i))
+
+
+def soft_max(a, b, c, d, e, f, g, h, i):
+    mx = np.maximum(np.maximum(np.maximum(d, e), f), np.maximum(b, h))
+    return mx + np.maximum(np.maximum(mx, a), np.maximum(np.maximum(c, g), i))
+
+
+def weighted_sum(b, d, f, h, e, w):
+    """b w + d w + f w + h w + e, summed left to right."""
+    return (((b * w + d * w) + f * w) + h * w) + e
+
+
 def cas_unit(x, peak):
     """CasFilter on a float32 [rows, cols, ch] frame of values in [0, 1]; returns the saturated float32 result."""
     a, b, c, d, e, f, g, h, i = _window(np.asarray(x, f32))
-    mn = np.minimum(np.minimum(np.minimum(d, e), f), np.minimum(b, h))
-    mx = np.maximum(np.maximum(np.maximum(d, e), f), np.maximum(b, h))
-    mn = mn + np.minimum(np.minimum(mn, a), np.minimum(np.minimum(c, g), i))
-    mx = mx + np.maximum(np.maximum(mx, a), np.maximum(np.maximum(c, g), i))
+    mn = soft_min(a, b, c, d, e, f, g, h, i)
+    mx = soft_max(a, b, c, d, e, f, g, h, i)
     amp = lo_sqrt(sat(np.minimum(mn, f32(2) - mx) * lo_rcp(mx)))
     w = amp * f32(peak)
-    num = (((b * w + d * w) + f * w) + h * w) + e
-    return sat(num * med_rcp(f32(1) + f32(4) * w))
+    return sat(weighted_sum(b, d, f, h, e, w) * med_rcp(f32(1) + f32(4) * w))
 
 
 def cas(img, sharpness=0.8):

@@ -162,6 +162,11 @@ def channel_bytes(fmt):
     return (2, 1, 0) if fmt in (FMT_BGR, FMT_BGRA) else (0, 1, 2)
 
 
+def luma(tr, tg, tb):
+    """Twice an approximate luma: 0.5 b + (0.5 r + g)."""
+    return tb * f32(0.5) + (tr * f32(0.5) + tg)
+
+
 def easu_unit(r, g, b, region, out_rows, out_cols, row_block=256):
     """FsrEasuF on float32 [H, W] planes r, g, b of values in [0, 1]; returns the float32 [out_rows, out_cols, 3] (r, g, b) result."""
     rows, cols = r.shape
@@ -186,7 +191,7 @@ def easu_unit(r, g, b, region, out_rows, out_cols, row_block=256):
                 ri = _texel_index(cy_all[gi][q][y0:y1], rows)[:, None]
                 ci = col_idx[name][None, :]
                 tr, tg, tb = r[ri, ci], g[ri, ci], b[ri, ci]
-                taps[name] = (tr, tg, tb, tb * f32(0.5) + (tr * f32(0.5) + tg))
+                taps[name] = (tr, tg, tb, luma(tr, tg, tb))
         out[y0:y1] = _easu_core(taps, px, ppy)
     return out
 

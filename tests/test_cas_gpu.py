@@ -117,6 +117,23 @@ def test_flat_frames_on_the_device(ctx, fmt):
         assert (out[1:-1, 1:-1, :3] == want_inner).all() and (out[0, :, :3] == want_border).all()
 
 
+def test_1080p_is_the_compiled_reference_shader(ctx):
+    """lvk_hip_cas against the reference's own shader text (oracle/_ref/libffx_ref.so: cas.effect's pixel shader and CasSetup) between the
+    specification's load and store, with no numpy filter in between."""
+    from tests import ffx_ref_lib
+    ref = ffx_ref_lib.load()
+    rows, cols, sharpness = 1080, 1920, 0.8
+    img = content(rows, cols, 3, seed=1080)
+    src = Buffer(rows, cols, 3, cols * 3, 0, 1, img)
+    dst = Buffer(rows, cols, 3, cols * 3, 0, 2)
+    assert run(ctx, src, dst, BGR, sharpness) == 0, ctx.lib.lvk_hip_last_error(ctx.handle)
+    ctx.sync()
+    y = ref.cas_unit(nc.UNIT[img], ref.peak(sharpness))
+    want = np.rint(y[..., :3] * np.float32(255)).astype(np.uint8)
+    got = dst.dev.cpu().numpy()[:rows * cols * 3].reshape(rows, cols, 3)
+    assert np.array_equal(got, want), "%d bytes differ" % int((got != want).sum())
+
+
 def test_refused_calls_leave_the_destination_untouched(ctx):
     import torch
     rows, cols = 9, 13

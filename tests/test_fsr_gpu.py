@@ -76,6 +76,29 @@ def test_frame_sizes(ctx, rows, cols, region, oh, ow, fmt):
     check(ctx, content(rows, cols, nf.CHANNELS[fmt], seed=rows + cols), fmt, region, oh, ow)
 
 
+@pytest.mark.parametrize("region,oh,ow", [((0, 0, 1920, 1080), 2160, 3840), ((480, 270, 960, 540), 1080, 1920)])
+def test_1080p_is_the_compiled_reference_shader(ctx, region, oh, ow):
+    """lvk_hip_fsr_easu against the reference's own shader text (oracle/_ref/libffx_ref.so: fsr.effect's EASU pixel shader and
+    FsrEasuCon) between the specification's load and store, with no numpy filter in between.  BGRA: the shader's r, g, b are bytes
+    2, 1, 0 and its 4th component is stored as it returns it."""
+    from tests import ffx_ref_lib
+    from tests.np_cas import UNIT
+    ref = ffx_ref_lib.load()
+    rows, cols = 1080, 1920
+    img = content(rows, cols, 4, seed=oh)
+    src = Buffer(rows, cols, 4, cols * 4, 0, 1, img)
+    dst = Buffer(oh, ow, 4, ow * 4, 0, 2)
+    assert run(ctx, src, dst, BGRA, region, oh, ow) == 0, ctx.lib.lvk_hip_last_error(ctx.handle)
+    ctx.sync()
+    x = UNIT[img]
+    y, dev = ref.easu_unit(x[..., 2], x[..., 1], x[..., 0], region, oh, ow)
+    assert dev < 0.25, dev
+    q = np.rint(y * np.float32(255)).astype(np.uint8)
+    want = np.stack([q[..., 2], q[..., 1], q[..., 0], q[..., 3]], -1)
+    got = dst.dev.cpu().numpy()[:oh * ow * 4].reshape(oh, ow, 4)
+    assert np.array_equal(got, want), "%d bytes differ" % int((got != want).sum())
+
+
 @pytest.mark.parametrize("src_pad,dst_pad", [(1, 13), (13, 64), (64, 1), (0, 13)])
 @pytest.mark.parametrize("src_off,dst_off", [(1, 2), (3, 0), (0, 3), (2, 1)])
 @pytest.mark.parametrize("fmt", [BGR, RGBA])
