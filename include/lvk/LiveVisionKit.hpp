@@ -637,6 +637,9 @@ public:
         return {r[0], r[1], r[2], r[3]};
     }
     const std::shared_ptr<hip::Context>& context() const { return m_Ctx; }
+    // VSFilter::draw_debug_hud (Sources/Stabilisation/VSFilter.cpp:368-383) into an output frame: "%.2fms (%.2fms)" at the stable region's
+    // corner, a magenta rectangle around the region.  On the device, asynchronous on the frame's context (defined in Drawing.hpp).
+    void draw_hud(VideoFrame& frame, double frame_time_ms, double deviation_ms, double timing_threshold_ms = 6.0) const;
 
     // ---- MI355X additions (no reference counterpart; the reference API above is unchanged) ----------------------------------
     // Overlap mode: the bulk kernels (4:2:0 conversion, output remap) run on a second stream next to the next frame's tracking
@@ -1056,3 +1059,6 @@ using GridDetectorSettings = FeatureDetectorSettings;
 
 // the OBS plugin's FSR filter (Sources/Scaling/FSRFilter.cpp, Effects/FSREffect.cpp)
 #include "FSRFilter.hpp"
+
+// Functions/Drawing.hpp: points, rectangles and text of the test-mode HUD
+#include "Drawing.hpp"

@@ -58,6 +58,13 @@ struct Scalar
     const double& operator[](int i) const { return val[i]; }
 };
 
+// the font argument of lvk::draw_text (imgproc.hpp values); the device font ignores it
+enum HersheyFonts
+{
+    FONT_HERSHEY_SIMPLEX = 0, FONT_HERSHEY_PLAIN = 1, FONT_HERSHEY_DUPLEX = 2, FONT_HERSHEY_COMPLEX = 3, FONT_HERSHEY_TRIPLEX = 4,
+    FONT_HERSHEY_COMPLEX_SMALL = 5, FONT_HERSHEY_SCRIPT_SIMPLEX = 6, FONT_HERSHEY_SCRIPT_COMPLEX = 7, FONT_ITALIC = 16,
+};
+
 constexpr int CV_8UC1_ = 0, CV_8UC3_ = 16, CV_8UC4_ = 24;
 
 // the cv::ColorConversionCodes that lvk::ConversionFilter takes (imgproc.hpp values)

@@ -61,7 +61,7 @@ const char* lvk_hip_last_error(lvk_hip_ctx* ctx);    /* NULL ctx: last error of 
 const char* lvk_hip_version(void);                   /* human-readable build string */
 /* ABI number of PART 1 of this header as the library was built (compare with LVK_HIP_ABI_VERSION of the header a host was compiled against;
  * tests/test_abi.py holds the two together). */
-#define LVK_HIP_ABI_VERSION 10
+#define LVK_HIP_ABI_VERSION 11
 int  lvk_hip_abi_version(void);
 /* Devices of this process: contexts are addressed by HIP device index, and lvk_hip_device_count() is the number of indices worth trying -- the
  * highest gfx950 index + 1 (0 when there is no gfx950 device; never an error).  On the usual host every index below it is an MI355X; on a mixed
@@ -260,6 +260,26 @@ int  lvk_hip_stab_draw_motion_mesh(lvk_hip_stab* stab);
 int  lvk_hip_draw_grid(lvk_hip_ctx* ctx, void* d_dst, int dst_step, int rows, int cols, int grid_w, int grid_h, const uint8_t colour[3], int thickness);
 int  lvk_hip_draw_crosses(lvk_hip_ctx* ctx, void* d_dst, int dst_step, int rows, int cols, const float* pts_xy, int n,
                           float scale_x, float scale_y, const uint8_t colour[3], int cross_size, int thickness);
+/* The test-mode HUD, drawn on the device (the reference maps the frame to the host for cv::rectangle / cv::putText): lvk::draw_points,
+ * lvk::draw_rect and lvk::draw_text (Functions/Drawing.tpp:40-49,95-141,198-218; VSFilter::draw_debug_hud, VSFilter.cpp:368-383), IN PLACE
+ * on a packed 8UC3 device frame of any pitch and byte alignment; only bytes inside cols * 3 of a row are written.  Asynchronous on the
+ * context's stream.  Whatever lies outside the frame is clipped; a call that draws nothing (n == 0, an empty string, a shape wholly outside
+ * the frame) is a valid no-op.  A refused call (LVK_HIP_ERR_ARG) leaves the frame untouched.  Specification: tests/np_draw.py.
+ *   points  the `points` kernel (Drawing.cl:43-69): pts_xy as for lvk_hip_draw_crosses; each point is the square of half width
+ *           (point_size + 1) / 2, x in [max(px - h, 0), min(px + h, cols)), y alike.  Refused: point_size < 1, a negative scale.
+ *   rect    rect_xywh = (x, y, w, h), corners (x0, y0) = (x, y), (x1, y1) = (x + w - 1, y + h - 1).  thickness t >= 1: with a = t / 2 and
+ *           b = (t - 1) / 2 the pixels of [x0 - a, x1 + b] x [y0 - a, y1 + b] that are not strictly inside (x0 + b, x1 - a) x (y0 + b, y1 - a);
+ *           t = 1 is the outline cv::rectangle(Rect) draws, above that the band has SQUARE corners where OpenCV rounds the joins of its
+ *           thick lines.  t < 0 fills the rectangle (cv::FILLED).  Refused: t == 0, w <= 0 or h <= 0, a call of 2^31 pixels or more.
+ *   text    the library's OWN fixed-cell font, not OpenCV's Hershey glyphs: 5 x 7 glyphs in a 6 x 9 cell for the bytes 0x20 .. 0x7E, any other
+ *           byte draws as '?'.  (x, y) is the bottom-left corner of the baseline as for cv::putText: font pixel (c, r) of character i is the
+ *           scale x scale block at (x + (6 i + c) scale, y - (7 - r) scale), grown by (thickness - 1) / 2 pixels on each side.  One launch a
+ *           string.  Refused: a string of more than 256 bytes, scale outside [1, 32767], thickness outside [1, 65535]. */
+int  lvk_hip_draw_points(lvk_hip_ctx* ctx, void* d_dst, int dst_step, int rows, int cols, const float* pts_xy, int n, float scale_x, float scale_y,
+                         const uint8_t colour[3], int point_size);
+int  lvk_hip_draw_rect(lvk_hip_ctx* ctx, void* d_dst, int dst_step, int rows, int cols, const int rect_xywh[4], const uint8_t colour[3], int thickness);
+int  lvk_hip_draw_text(lvk_hip_ctx* ctx, void* d_dst, int dst_step, int rows, int cols, const char* text, int x, int y, const uint8_t colour[3],
+                       int scale, int thickness);
 /* Fused lens pre-warp for the stream this filter stabilizes: frames are pushed RAW (uncorrected); the tracker estimates the
  * motion between lens-corrected feature positions and the output remap composes lens map and stabilizing warp.
  * params = NULL switches it off.  Restarts the filter (queued frames are dropped). */
@@ -438,6 +458,10 @@ int  lvk_hip_fsr_easu(lvk_hip_ctx* ctx, const void* d_src, int src_step, int row
  * that is not > 0 (when used), a NULL pointer. */
 int  lvk_hip_fsr_geometry(int rows, int cols, int out_rows, int out_cols, float multiplier, int maintain_aspect_ratio, const int crop_ltrb[4],
                           int region_xywh[4], int out_rows_cols[2], int* skip);
+/* The box lvk_hip_draw_text draws into, host only (cv::getTextSize's place): wh = ((6 n - 1) scale + 2 g, 7 scale + 2 g) for n bytes and
+ * g = (thickness - 1) / 2, width 0 for an empty string; its top-left corner lies at (x - g, y - 7 scale - g).  *baseline = scale + g: what the
+ * cell keeps below y.  Refused like lvk_hip_draw_text, and for a NULL pointer. */
+int  lvk_hip_text_size(const char* text, int scale, int thickness, int wh[2], int* baseline);
 
 
 /* =====================================================================================================================================

@@ -11,7 +11,9 @@ from .deblocking import DeblockingFilter, DeblockingFilterSettings
 from .cas import CASFilter
 from .convert import ConversionFilter, reformat
 from .fsr import FSRFilter, fsr_geometry, easu_const
+from .draw import draw_points, draw_rect, draw_text, text_size
 from . import shard
 
 __all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "CASFilter",
-           "ConversionFilter", "reformat", "FSRFilter", "fsr_geometry", "easu_const", "_native"]
+           "ConversionFilter", "reformat", "FSRFilter", "fsr_geometry", "easu_const", "draw_points", "draw_rect",
+           "draw_text", "text_size", "_native"]

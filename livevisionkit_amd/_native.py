@@ -55,6 +55,11 @@ _SIG = {
     "lvk_hip_draw_grid": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_uint8), _c.c_int]),
     "lvk_hip_draw_crosses": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_float, _c.c_float,
                                         _c.POINTER(_c.c_uint8), _c.c_int, _c.c_int]),
+    "lvk_hip_draw_points": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_float, _c.c_float,
+                                       _c.POINTER(_c.c_uint8), _c.c_int]),
+    "lvk_hip_draw_rect": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint8), _c.c_int]),
+    "lvk_hip_draw_text": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_char_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_uint8), _c.c_int, _c.c_int]),
+    "lvk_hip_text_size": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "lvk_hip_warpmesh_apply_yuv420": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int,
                                                  _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.POINTER(_c.c_uint8)]),
     "lvk_hip_warpmesh_apply": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int,
