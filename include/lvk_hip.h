@@ -602,6 +602,46 @@ int lvk_hip_estimate_global_motion(lvk_hip_ctx* ctx, const float* pts1, const fl
  * leaves them.  Host arrays (n x 2 floats, n bytes); returns the number of pairs kept (>= 0) or LVK_HIP_ERR_*. */
 int lvk_hip_fast_filter(lvk_hip_ctx* ctx, const float* prev, const float* matched, const uint8_t* status, int n, float* out_prev, float* out_matched);
 
+/* The tracker's chain optical flow -> fast_filter -> robust global motion (Vision/FrameTracker.cpp:140-168, 325-375) through the SAME launcher
+ * the stabilization filter enqueues it with, in a variant the caller selects; synchronous, per-call allocations (a test entry).
+ *   start       d_prev_img == NULL: from a flow result -- prev / matched (n_bound x 2 floats), status (n_bound bytes) and optionally und, the
+ *               lens-corrected positions (previous | matched), 2 x n_eff x 2 floats with n_eff = the effective count (below).
+ *               d_prev_img != NULL: from two device images (rows x cols, 8UC1) and prev: the flow kernel runs in its chained form (points read
+ *               from pinned host memory; with `lens` -- a profile for a lens_rows x lens_cols frame, lens_sx / lens_sy = frame / tracking size --
+ *               it writes the corrected positions itself).
+ *   compaction  separate_compact == 0: as the filter decides (inside the RANSAC's first kernel up to 2048 points, a kernel of its own beyond);
+ *               != 0: a kernel of its own for any n_bound.
+ *   count       count_on_device == 0: n_bound points.  != 0: the kernels read n_word from device memory and clamp it to [0, n_bound]
+ *               (n_eff); n_bound is the launch bound.
+ *   model       model_on_device == 0: `full` (homography / similarity).  != 0: the kernels read full_word from device memory, `full` is ignored.
+ *   completion  host_signal == 0: stream synchronisation.  != 0: the last kernel stores a word in host memory and the entry reads H, the
+ *               code, the mask and the host mirrors once it has seen it, as the filter does (signalled = 1; 0: the word came late).
+ * Results: H, rc (inlier count, or -12: no model -- fewer pairs than the model needs included, the count being the device's); mask (n_bound
+ * bytes, the first count meaningful); pairs_dev = the compacted pairs in device memory (p1 | p2, 2 x n_bound x 2 floats) and count_dev;
+ * count_host, mirror_matched, mirror_status = the host mirrors; when the flow ran, next_pts / flow_status (n_bound + 2 GUARD entries) and
+ * flow_und (2 n_bound + 2 GUARD entries; may be NULL without `lens`): the kernel's output buffers with GUARD entries in front and behind.
+ * Every output byte no kernel wrote holds LVK_TRACK_CHAIN_FILL. */
+#define LVK_TRACK_CHAIN_GUARD 64
+#define LVK_TRACK_CHAIN_FILL  0xA5
+typedef struct lvk_track_chain_desc
+{
+    const float* prev; const float* matched; const uint8_t* status; const float* und;
+    const void* d_prev_img; int prev_step; const void* d_next_img; int next_step; int rows, cols;
+    int win_w, win_h, max_level, max_count; double epsilon, min_eig;
+    const lvk_camera_params* lens; int lens_rows, lens_cols; double lens_sx, lens_sy;
+    int n_bound, count_on_device, n_word;
+    int full, model_on_device, full_word;
+    int separate_compact, host_signal;
+    double threshold; int region_w, region_h;
+} lvk_track_chain_desc;
+typedef struct lvk_track_chain_result
+{
+    double H[9]; int rc, signalled, count_dev, count_host;
+    uint8_t* mask; float* pairs_dev; float* mirror_matched; uint8_t* mirror_status;
+    float* next_pts; uint8_t* flow_status; float* flow_und;
+} lvk_track_chain_result;
+int lvk_hip_track_chain(lvk_hip_ctx* ctx, const lvk_track_chain_desc* desc, lvk_track_chain_result* result);
+
 /* Deblocking tap: the block grids of the last apply (synchronises the context's stream).  mean = the 8U block means, grid = the 8U mean absolute
  * deviations from them, keep_block = float(min(grid, L) * (1.0 / L)); ex * ey values each, row-major (NULL: skipped).  extent_xy = (ex, ey).
  * Returns ex * ey, or LVK_HIP_ERR_ARG before the first apply or when capacity < ex * ey. */

@@ -20,6 +20,33 @@ def _u8x3(bg):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
 
+TRACK_CHAIN_GUARD = 64        # LVK_TRACK_CHAIN_GUARD: entries in front of and behind the flow kernel's output buffers
+TRACK_CHAIN_FILL = 0xA5       # LVK_TRACK_CHAIN_FILL: every output byte no kernel wrote
+
+
+class TrackChainDesc(ctypes.Structure):
+    """lvk_track_chain_desc (include/lvk_hip.h, PART 2)."""
+    _fields_ = [("prev", ctypes.POINTER(ctypes.c_float)), ("matched", ctypes.POINTER(ctypes.c_float)), ("status", ctypes.POINTER(ctypes.c_uint8)),
+                ("und", ctypes.POINTER(ctypes.c_float)),
+                ("d_prev_img", ctypes.c_void_p), ("prev_step", ctypes.c_int), ("d_next_img", ctypes.c_void_p), ("next_step", ctypes.c_int),
+                ("rows", ctypes.c_int), ("cols", ctypes.c_int),
+                ("win_w", ctypes.c_int), ("win_h", ctypes.c_int), ("max_level", ctypes.c_int), ("max_count", ctypes.c_int),
+                ("epsilon", ctypes.c_double), ("min_eig", ctypes.c_double),
+                ("lens", ctypes.c_void_p), ("lens_rows", ctypes.c_int), ("lens_cols", ctypes.c_int), ("lens_sx", ctypes.c_double), ("lens_sy", ctypes.c_double),
+                ("n_bound", ctypes.c_int), ("count_on_device", ctypes.c_int), ("n_word", ctypes.c_int),
+                ("full", ctypes.c_int), ("model_on_device", ctypes.c_int), ("full_word", ctypes.c_int),
+                ("separate_compact", ctypes.c_int), ("host_signal", ctypes.c_int),
+                ("threshold", ctypes.c_double), ("region_w", ctypes.c_int), ("region_h", ctypes.c_int)]
+
+
+class TrackChainResult(ctypes.Structure):
+    """lvk_track_chain_result (include/lvk_hip.h, PART 2)."""
+    _fields_ = [("H", ctypes.c_double * 9), ("rc", ctypes.c_int), ("signalled", ctypes.c_int), ("count_dev", ctypes.c_int), ("count_host", ctypes.c_int),
+                ("mask", ctypes.POINTER(ctypes.c_uint8)), ("pairs_dev", ctypes.POINTER(ctypes.c_float)), ("mirror_matched", ctypes.POINTER(ctypes.c_float)),
+                ("mirror_status", ctypes.POINTER(ctypes.c_uint8)),
+                ("next_pts", ctypes.POINTER(ctypes.c_float)), ("flow_status", ctypes.POINTER(ctypes.c_uint8)), ("flow_und", ctypes.POINTER(ctypes.c_float))]
+
+
 class Context:
     """One HIP stream + staging on one GPU (reference analogue: the implicit cv::ocl queue)."""
 
@@ -347,6 +374,59 @@ class Context:
         if m < 0:
             self._check(m)
         return oa[:m], ob[:m]
+
+    def track_chain(self, prev, matched=None, status=None, und=None, images=None, win=(11, 11), max_level=3, max_count=5, epsilon=0.01, min_eig=1e-4,
+                    lens=None, threshold=3.0, region=(480, 270), full=True, full_word=None, n_word=None, separate_compact=False, host_signal=False):
+        """The tracker's chain (optical flow ->) fast_filter -> global motion through the launcher the stabilization filter uses (lvk_hip_track_chain).
+        Starts from a flow result (prev, matched, status[, und = corrected (previous | matched) positions]) or from images = (prev, next) device
+        tensors; lens = (params, frame_rows, frame_cols, sx, sy).  n_word / full_word: the count / the model choice travel in device memory
+        (len(prev) is then the launch bound, `full` a placeholder the word overrides).  Returns a dict of everything the entry reports."""
+        fp, bp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)
+        prev = np.ascontiguousarray(prev, np.float32).reshape(-1, 2)
+        nb, G = len(prev), TRACK_CHAIN_GUARD
+        d, r = TrackChainDesc(), TrackChainResult()
+        keep = [prev]
+        d.prev = prev.ctypes.data_as(fp)
+        if images is None:
+            matched = np.ascontiguousarray(matched, np.float32).reshape(nb, 2); status = np.ascontiguousarray(status, np.uint8).reshape(nb)
+            keep += [matched, status]
+            d.matched = matched.ctypes.data_as(fp); d.status = status.ctypes.data_as(bp)
+            if und is not None:
+                und = np.ascontiguousarray(und, np.float32).reshape(-1, 2)
+                n_eff = nb if n_word is None else min(max(int(n_word), 0), nb)
+                if len(und) != 2 * n_eff:
+                    raise ValueError("und holds 2 x the effective count of positions (previous | matched)")
+                keep.append(und)
+                d.und = und.ctypes.data_as(fp)
+        else:
+            a, b = images
+            keep += [a, b]
+            d.d_prev_img = a.data_ptr(); d.prev_step = a.stride(0); d.d_next_img = b.data_ptr(); d.next_step = b.stride(0)
+            d.rows, d.cols = a.shape[0], a.shape[1]
+            d.win_w, d.win_h, d.max_level, d.max_count, d.epsilon, d.min_eig = win[0], win[1], max_level, max_count, float(epsilon), float(min_eig)
+            if lens is not None:
+                params, lrows, lcols, sx, sy = lens
+                arr = (ctypes.c_double * 9)(*[float(v) for v in params])
+                keep.append(arr)
+                d.lens = ctypes.cast(arr, ctypes.c_void_p); d.lens_rows, d.lens_cols, d.lens_sx, d.lens_sy = int(lrows), int(lcols), float(sx), float(sy)
+        d.n_bound = nb
+        d.count_on_device, d.n_word = (0, 0) if n_word is None else (1, int(n_word))
+        d.full = 1 if full else 0
+        d.model_on_device, d.full_word = (0, 0) if full_word is None else (1, int(full_word))
+        d.separate_compact = 1 if separate_compact else 0; d.host_signal = 1 if host_signal else 0
+        d.threshold = float(threshold); d.region_w, d.region_h = int(region[0]), int(region[1])
+        mask = np.zeros(nb, np.uint8); pairs = np.zeros((2, nb, 2), np.float32); mm = np.zeros((nb, 2), np.float32); ms = np.zeros(nb, np.uint8)
+        r.mask = mask.ctypes.data_as(bp); r.pairs_dev = pairs.ctypes.data_as(fp); r.mirror_matched = mm.ctypes.data_as(fp); r.mirror_status = ms.ctypes.data_as(bp)
+        out = {}
+        if images is not None:
+            nxt = np.zeros((nb + 2 * G, 2), np.float32); fst = np.zeros(nb + 2 * G, np.uint8); fund = np.zeros((2 * nb + 2 * G, 2), np.float32)
+            r.next_pts = nxt.ctypes.data_as(fp); r.flow_status = fst.ctypes.data_as(bp); r.flow_und = fund.ctypes.data_as(fp)
+            out.update(next_pts=nxt, flow_status=fst, flow_und=fund)
+        self._check(self.lib.lvk_hip_track_chain(self.handle, ctypes.byref(d), ctypes.byref(r)))
+        del keep
+        out.update(H=np.array(r.H, np.float64).reshape(3, 3), rc=r.rc, signalled=r.signalled, count_dev=r.count_dev, count_host=r.count_host, mask=mask,
+                   pairs_dev=pairs, mirror_matched=mm, mirror_status=ms)
+        return out
 
     def warpmesh_apply_yuv420(self, src, mesh, bg=(255, 0, 255), nv12=False):
         """WarpMesh::apply + 4:2:0 egress in one kernel: packed YUV [rows, cols, 3] -> (y, u, v) I420 or (y, uv) NV12 planes."""

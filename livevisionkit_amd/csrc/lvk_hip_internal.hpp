@@ -285,6 +285,33 @@ int lvk_launch_compact_ransac(lvk_hip_ctx* ctx, const float2* d_prev, const floa
                               double threshold, double region_w, double region_h, bool full_homography, void* d_ws, double* d_H, int* d_ninl, uint8_t* d_mask,
                               const int* d_n_raw = nullptr, const int* d_full = nullptr, LvkHostSignal done = LvkHostSignal{nullptr, 0});
 
+// The tracker's chained block as ONE launcher (track_chain.hip): optical flow -> fast_filter -> robust global motion on ctx->stream, no host
+// round trip in between.  lvk_hip_stab::track and the diagnostics entry lvk_hip_track_chain both enqueue the chain through it -- and nothing else
+// calls lvk_launch_match_compact, lvk_launch_compact_ransac or the chained form of lvk_launch_pyrlk --, so what the tests drive is what the filter runs.
+struct LvkTrackChain
+{
+    // optical flow; prev_pyr == nullptr: (d_pts, d_matched, d_status, d_und) hold a flow result already
+    const PyrArgs* prev_pyr = nullptr; const PyrArgs* next_pyr = nullptr;
+    const float2* h_pts = nullptr;                  // the tracked points, device-visible host memory (the flow kernel leaves a copy in d_pts)
+    int win_w = 0, win_h = 0, max_count = 0; double epsilon = 0.0, min_eig = 0.0;
+    const LensModel* lens = nullptr; double lens_sx = 0.0, lens_sy = 0.0;        // fused lens mode: the flow kernel writes d_und itself
+    int n = 0; const int* d_n = nullptr;            // number of tracked points; d_n: it lives on the device, n is the launch's upper bound
+    bool full = false; const int* d_full = nullptr; // homography / similarity; d_full: the choice lives on the device (`full` ignored)
+    float2* d_pts = nullptr; float2* d_matched = nullptr; uint8_t* d_status = nullptr;
+    float2* d_und = nullptr;                        // lens-corrected (previous | matched), 2 n entries; nullptr: the raw positions are the pairs
+    float2* d_p1 = nullptr; float2* d_p2 = nullptr; int* d_count = nullptr;      // the compacted pairs and their count
+    int* h_count = nullptr; float2* h_matched = nullptr; uint8_t* h_status = nullptr;      // host mirrors (device-visible host memory)
+    int region_w = 0, region_h = 0; double threshold = 0.0;
+    // field preset / comparisons: fast_filter as a kernel of its own also where the hypotheses kernel could compact (n <= LVK_COMPACT_RANSAC_MAX)
+    bool separate_compact = false;
+    bool estimate = true;                           // false: the chain ends behind fast_filter (the field preset solves its mesh from the pairs)
+    void* d_ws = nullptr; double* h_H = nullptr; int* h_ninl = nullptr; uint8_t* h_mask = nullptr;
+    LvkHostSignal done{nullptr, 0};
+    // called between the flow stage (optical flow + stand-alone fast_filter) and the motion stage: the stabilizer's per-stage profiling
+    void (*stage_boundary)(void* user) = nullptr; void* user = nullptr;
+};
+int lvk_launch_track_chain(lvk_hip_ctx* ctx, const LvkTrackChain& c);
+
 struct LensArgs;
 // Dense remap on an explicit stream (remap.hip)
 int lvk_launch_remap_homography(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,

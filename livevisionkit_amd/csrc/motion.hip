@@ -934,7 +934,11 @@ int lvk_hip_fast_filter(lvk_hip_ctx* ctx, const float* prev, const float* matche
         (e = hipMemcpyAsync(d + n, matched, n * sizeof(float2), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(d_s, status, n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
     { cleanup(); return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(e)); }
-    int rc = lvk_launch_match_compact(ctx, d, d + n, d_s, n, d + 2 * n, d + 3 * n, d_c, h_c, h_m, h_s, nullptr, 0.0f, 0.0f);
+    // (the chain's launcher, ended behind fast_filter: the kernel the filter launches for the field preset and beyond LVK_COMPACT_RANSAC_MAX points)
+    LvkTrackChain c;
+    c.n = n; c.d_pts = d; c.d_matched = d + n; c.d_status = d_s; c.d_p1 = d + 2 * n; c.d_p2 = d + 3 * n; c.d_count = d_c;
+    c.h_count = h_c; c.h_matched = h_m; c.h_status = h_s; c.separate_compact = true; c.estimate = false;
+    int rc = lvk_launch_track_chain(ctx, c);
     int m = 0;
     if (rc == LVK_HIP_OK)
     {

@@ -273,7 +273,9 @@ void k_pyrlk(PyrArgs prev, PyrArgs next, const float2* __restrict__ prev_pts, fl
     const int level_bytes = WIN ? (int)lvk_pyrlk_part_offset(WIN, WIN) : level_bytes_arg;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int pt = blockIdx.x;                                                // grid = n
-    if (la.n_dev) { n = *la.n_dev; if (pt >= n) return; }                      // (workgroup-uniform: before any barrier)
+    // (clamped to the launch bound like k_match_compact / k_ransac_hypotheses do: `n` is also where the matched half of `und` begins, and a
+    //  word above the bound must not move it behind the 2 n entries the buffer has)
+    if (la.n_dev) { n = min(max(*la.n_dev, 0), n); if (pt >= n) return; }      // (workgroup-uniform: before any barrier)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tw = win_w + 1, th = win_h + 1, area = win_w * win_h, tarea = tw * th;
     const int jw = tw + 2 * LK_MARGIN, jh = th + 2 * LK_MARGIN;               // next-frame window incl. search margin

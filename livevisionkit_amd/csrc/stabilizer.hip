@@ -139,26 +139,26 @@ int lvk_hip_stab::track(const QueuedFrame& f, const void* luma, int luma_step, i
     {
         // fused lens mode: the motion is estimated between lens-corrected positions (what the reference chain LC -> VS tracks); the flow
         // kernel writes them itself (d_und: previous | matched)
-        if ((rc = lvk_launch_pyrlk(ctx, P.args, C.args, h_pts, n, d_matched, d_status, LK_WIN, LK_WIN, LK_ITERS, LK_EPS, LK_MIN_EIG, d_pts,
-                                   lens ? &lens_model : nullptr, (double)f.cols / (double)cur_w, (double)f.rows / (double)cur_h, lens ? d_und : nullptr, dn)) != LVK_HIP_OK) return rc;
-        const bool fused_compact = !field && n <= LVK_COMPACT_RANSAC_MAX;        // the RANSAC's first kernel compacts the flow result itself
-        if (!fused_compact && (rc = lvk_launch_match_compact(ctx, d_pts, d_matched, d_status, n, d_p1, d_p1 + cap_features, d_count, h_count, h_matched, h_status,
-                                                             lens ? d_und : nullptr, (float)cur_w, (float)cur_h, dn)) != LVK_HIP_OK) return rc;
-        prof_end(pe);
-        pe = prof_begin(LVK_STAGE_MOTION);
+        struct Stage { lvk_hip_stab* self; int* pe; } stage{this, &pe};
+        LvkTrackChain c;
+        c.prev_pyr = &P.args; c.next_pyr = &C.args; c.h_pts = h_pts;
+        c.win_w = LK_WIN; c.win_h = LK_WIN; c.max_count = LK_ITERS; c.epsilon = LK_EPS; c.min_eig = LK_MIN_EIG;
+        c.lens = lens ? &lens_model : nullptr; c.lens_sx = (double)f.cols / (double)cur_w; c.lens_sy = (double)f.rows / (double)cur_h;
+        c.n = n; c.d_n = dn; c.full = full; c.d_full = dfull;
+        c.d_pts = d_pts; c.d_matched = d_matched; c.d_status = d_status; c.d_und = lens ? d_und : nullptr;
+        c.d_p1 = d_p1; c.d_p2 = d_p1 + cap_features; c.d_count = d_count; c.h_count = h_count; c.h_matched = h_matched; c.h_status = h_status;
+        c.region_w = cur_w; c.region_h = cur_h; c.threshold = s.acceptance_threshold;
+        c.separate_compact = field; c.estimate = !field;
+        c.d_ws = d_ransac_ws; c.h_H = h_H; c.h_ninl = h_ninl; c.h_mask = h_mask; c.done = done;
+        c.stage_boundary = [](void* u) { Stage* g = (Stage*)u; g->self->prof_end(*g->pe); *g->pe = g->self->prof_begin(LVK_STAGE_MOTION); };
+        c.user = &stage;
+        if ((rc = lvk_launch_track_chain(ctx, c)) != LVK_HIP_OK) return rc;
         if (field)
         {
             // estimate_local_motions (FrameTracker.cpp:200-321): least-squares mesh through the matches, solved on the device
             if ((rc = lvk_launch_mesh_solve(mesh_dev, st, d_mesh_scratch, d_p1, d_p1 + cap_features, d_count, n, s.min_motion_samples, (float)cur_w, (float)cur_h,
                                             s.temporal_smoothing, s.acceptance_threshold, h_offsets, h_mask, h_mesh_status)) != LVK_HIP_OK) return rc;
         }
-        else if (fused_compact)
-        {
-            if ((rc = lvk_launch_compact_ransac(ctx, d_pts, d_matched, d_status, n, d_p1, d_p1 + cap_features, d_count, h_count, h_matched, h_status,
-                                                lens ? d_und : nullptr, (float)cur_w, (float)cur_h,
-                                                s.acceptance_threshold, (double)cur_w, (double)cur_h, full, d_ransac_ws, h_H, h_ninl, h_mask, dn, dfull, done)) != LVK_HIP_OK) return rc;
-        }
-        else if ((rc = lvk_launch_ransac(ctx, d_p1, d_p1 + cap_features, n, s.acceptance_threshold, (double)cur_w, (double)cur_h, full, d_ransac_ws, h_H, h_ninl, h_mask, d_count, dfull, done)) != LVK_HIP_OK) return rc;
         prof_end(pe);
     }
     else

@@ -40,6 +40,23 @@ def test_global_motion_bit_exact(ctx, oracle, partial):
             assert rc_o == rc_g, (n, rc_o, rc_g)
         assert np.array_equal(m_o, m_g), n
         assert np.array_equal(H_o.view(np.uint64), H_g.view(np.uint64)), (n, np.abs(H_o - H_g).max())
+    # the unfused host-count kernels on both sides of the wave (64), block (256 / 512) and LDS_POINTS (2048) multiples: the strided partial
+    # sums and the switch between the staged and the global-memory kernels, two motions, the tightest and the widest threshold
+    from tests import track_chain_ref as T
+    for n in T.N_EDGES:
+        for motion, thr in (("perspective", 0.5), ("rotzoom", 20.0)):
+            p1 = np.c_[rng.uniform(0, 480, n), rng.uniform(0, 270, n)].astype(np.float32)
+            p2 = T.apply_h(T.motion_matrix(motion, (480, 270), not partial), p1) + rng.normal(0, 0.2, p1.shape)
+            out = rng.random(n) < 0.3
+            p2[out] += rng.uniform(-40, 40, (out.sum(), 2))
+            p2 = p2.astype(np.float32)
+            rc_o, H_o, m_o = oracle.find_homography(p1, p2, thr, partial=partial)
+            rc_g, H_g, m_g = ctx.estimate_global_motion(p1, p2, thr, full_homography=not partial)
+            assert (rc_o < 0) == (rc_g < 0), (n, motion, thr, rc_o, rc_g)
+            if rc_o >= 0:
+                assert rc_o == rc_g, (n, motion, thr, rc_o, rc_g)
+            assert np.array_equal(m_o, m_g), (n, motion, thr)
+            assert np.array_equal(H_o.view(np.uint64), H_g.view(np.uint64)), (n, motion, thr, np.abs(H_o - H_g).max())
 
 
 def test_global_motion_degenerate_inputs(ctx, oracle):

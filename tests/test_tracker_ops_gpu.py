@@ -5,6 +5,7 @@ import pytest
 
 from tests import synth
 from tests.test_oracle_imgproc import _smooth_scene
+from tests.track_chain_ref import swap_erase as _swap_erase
 
 pytestmark = pytest.mark.gpu
 
@@ -186,18 +187,6 @@ def test_luma_area_resize_bgr_rgb(ctx, oracle, src_size, dst_size, channel):
     got = ctx.luma_area_resize(_gpu(frame), *dst_size, channel=channel)
     ctx.sync()
     assert np.array_equal(got.cpu().numpy(), want)
-
-
-def _swap_erase(arrays, keep):
-    """fast_filter (Functions/Container.tpp:97-121): back to front, swap a dropped element with the last kept one."""
-    arrays = [a.copy() for a in arrays]
-    m = len(keep)
-    for k in range(len(keep) - 1, -1, -1):
-        if not keep[k]:
-            m -= 1
-            for a in arrays:
-                a[[k, m]] = a[[m, k]]
-    return [a[:m] for a in arrays]
 
 
 @pytest.mark.parametrize("n", [1, 2, 7, 64, 257, 1856, 3728, 4096])
