@@ -12,7 +12,7 @@
 //
 // Transfers: like the reference (one bulk cv::Mat::copyTo(UMat) of the planes' contiguous span, blocking, FrameIngest.cpp:362-474) the upload has
 // finished with the host planes when it returns, and the download has filled them.  Hosts that own pinned planes and want the transfers scheduled
-// around the filter use lvk_hip_stab_push_yuv420_host instead (HostFrame420).
+// around the filter use lvk_hip_stab_push_yuv420_host (HostFrame420) or, for every other format, lvk_hip_stab_push_obs_host (HostFrameOBS) instead.
 #pragma once
 
 #include "LiveVisionKit.hpp"

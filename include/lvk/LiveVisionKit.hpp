@@ -308,6 +308,68 @@ private:
     std::shared_ptr<hip::Context> m_ctx;
 };
 
+// One frame of ANY OBS video format FrameIngest::Select accepts (except Y800) in pinned host memory, laid out as obs_source_frame lays it out:
+// data[] / linesize[] of the planes FrameIngest moves, one after the other in one block (the alpha planes of I40A / I42A / YUVA are not part of it).
+// StabilizationFilter::apply takes it directly (lvk_hip_stab_push_obs_host).
+struct HostFrameOBS
+{
+    uint64_t timestamp = 0;
+    int format = 0;                                   // LVK_VIDEO_FORMAT_* = libobs' enum video_format
+    int cols = 0, rows = 0;
+    uint8_t* data[3] = {nullptr, nullptr, nullptr};
+    int linesize[3] = {0, 0, 0};
+
+    // rows and bytes per row of the planes of one frame; returns their number (0: not a format of this struct)
+    static int plane_table(int format, int rows, int cols, int prow[3], int pbytes[3])
+    {
+        auto set = [&](int i, int r, int w) { prow[i] = r; pbytes[i] = w; };
+        switch (format)
+        {
+        case LVK_VIDEO_FORMAT_I420: case LVK_VIDEO_FORMAT_I40A: set(0, rows, cols); set(1, rows / 2, cols / 2); set(2, rows / 2, cols / 2); return 3;
+        case LVK_VIDEO_FORMAT_NV12: set(0, rows, cols); set(1, rows / 2, cols); return 2;
+        case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A: set(0, rows, cols); set(1, rows, cols / 2); set(2, rows, cols / 2); return 3;
+        case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA: set(0, rows, cols); set(1, rows, cols); set(2, rows, cols); return 3;
+        case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: case LVK_VIDEO_FORMAT_UYVY: set(0, rows, 2 * cols); return 1;
+        case LVK_VIDEO_FORMAT_AYUV: case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX: set(0, rows, 4 * cols); return 1;
+        case LVK_VIDEO_FORMAT_BGR3: set(0, rows, 3 * cols); return 1;
+        default: return 0;
+        }
+    }
+
+    bool empty() const { return !m_buf || cols == 0 || rows == 0; }
+    void release() { m_buf.reset(); cols = rows = 0; for (int i = 0; i < 3; i++) { data[i] = nullptr; linesize[i] = 0; } }
+    void create(const cv::Size& sz, int obs_format, const std::shared_ptr<hip::Context>& ctx = nullptr)
+    {
+        int prow[3] = {0, 0, 0}, pbytes[3] = {0, 0, 0};
+        const int n = plane_table(obs_format, sz.height, sz.width, prow, pbytes);
+        LVK_HIP_ASSERT(n > 0 && sz.width > 0 && sz.height > 0);
+        if (m_buf && m_buf.use_count() == 1 && cols == sz.width && rows == sz.height && format == obs_format && (!ctx || ctx == m_ctx)) return;
+        m_ctx = ctx ? ctx : (m_ctx ? m_ctx : hip::shared_context());
+        size_t total = 0;
+        for (int i = 0; i < n; i++) total += (size_t)prow[i] * pbytes[i];
+        void* p = nullptr;
+        m_ctx->check(lvk_hip_host_malloc(m_ctx->get(), total, &p), "HostFrameOBS::create");
+        auto c = m_ctx;
+        m_buf = std::shared_ptr<void>(p, [c](void* q) { lvk_hip_host_free(c->get(), q); });
+        cols = sz.width; rows = sz.height; format = obs_format; m_bytes = total;
+        uint8_t* q = static_cast<uint8_t*>(p);
+        for (int i = 0; i < 3; i++)
+        {
+            data[i] = i < n ? q : nullptr; linesize[i] = i < n ? pbytes[i] : 0;
+            if (i < n) q += (size_t)prow[i] * pbytes[i];
+        }
+    }
+    size_t bytes() const { return m_bytes; }
+    bool unique() const { return m_buf && m_buf.use_count() == 1; }
+    // an output of StabilizationFilter::apply is complete once its filter's context is idle
+    void wait() const { if (m_ctx) { hip::ContextLock lock(m_ctx->mutex()); m_ctx->check(lvk_hip_sync(m_ctx->get()), "HostFrameOBS::wait"); } }
+    const std::shared_ptr<hip::Context>& context() const { return m_ctx; }
+private:
+    std::shared_ptr<void> m_buf;
+    std::shared_ptr<hip::Context> m_ctx;
+    size_t m_bytes = 0;
+};
+
 // ---------------------------------------------------------------------------------------------- Timing
 class Time
 {
@@ -725,6 +787,32 @@ public:
         else output.release();
         sync_gpu(profile);
     }
+    // The same for a host frame of any OBS video format (lvk_hip_stab_push_obs_host): `input` is consumed when the call returns; `output` -- the DELAYED
+    // frame at its own size, in the input's format; released while the delay builds -- is complete after output.wait() or a profiled call.
+    void apply(const HostFrameOBS& input, HostFrameOBS& output, const bool profile = false)
+    {
+        LVK_HIP_ASSERT(!input.empty());
+        hip::ContextLock lock(m_Ctx->mutex());
+        sync_gpu(profile);
+        m_LastRows = input.rows; m_LastCols = input.cols;
+        const int ffmt = lvk_hip_obs_frame_format(input.format);
+        lvk_frame_info due{input.rows, input.cols, ffmt};
+        if (lvk_hip_stab_next_output(m_Stab, input.rows, input.cols, ffmt, &due) != 1) due = lvk_frame_info{input.rows, input.cols, ffmt};
+        HostFrameOBS* slot = nullptr;
+        for (auto& f : m_HostPoolOBS) if (f.unique() && f.cols == due.cols && f.rows == due.rows && f.format == input.format) { slot = &f; break; }
+        if (!slot) { if (m_HostPoolOBS.size() >= 8) m_HostPoolOBS.erase(m_HostPoolOBS.begin()); m_HostPoolOBS.emplace_back(); slot = &m_HostPoolOBS.back(); }
+        slot->create({due.cols, due.rows}, input.format, m_Ctx);
+        HostFrameOBS result = *slot;
+        int produced = 0; uint64_t ts = 0;
+        const void* const in_planes[3] = {input.data[0], input.data[1], input.data[2]};
+        void* const out_planes[3] = {result.data[0], result.data[1], result.data[2]};
+        m_Ctx->check(lvk_hip_stab_push_obs_host(m_Stab, input.format, in_planes, input.linesize, input.rows, input.cols, input.timestamp,
+                                                out_planes, result.linesize, result.rows, &produced, &ts, nullptr),
+                     "StabilizationFilter::apply(host OBS frame)");
+        if (produced) { result.timestamp = ts; output = std::move(result); }
+        else output.release();
+        sync_gpu(profile);
+    }
     void prefetch(const HostFrame420& next)
     {
         LVK_HIP_ASSERT(!next.empty());
@@ -816,6 +904,7 @@ private:
     struct HeldFrame { std::shared_ptr<void> buffer; std::shared_ptr<hip::Context> ctx; };
     int m_Device = 0;
     std::vector<HostFrame420> m_HostPool;
+    std::vector<HostFrameOBS> m_HostPoolOBS;
     std::shared_ptr<hip::Context> m_Ctx, m_BulkCtx, m_OutCtx;      // m_OutCtx: the context (stream) output frames are produced on
     lvk_hip_stab* m_Stab = nullptr;
     bool m_Overlap = false;

@@ -61,7 +61,7 @@ const char* lvk_hip_last_error(lvk_hip_ctx* ctx);    /* NULL ctx: last error of 
 const char* lvk_hip_version(void);                   /* human-readable build string */
 /* ABI number of PART 1 of this header as the library was built (compare with LVK_HIP_ABI_VERSION of the header a host was compiled against;
  * tests/test_abi.py holds the two together). */
-#define LVK_HIP_ABI_VERSION 11
+#define LVK_HIP_ABI_VERSION 12
 int  lvk_hip_abi_version(void);
 /* Devices of this process: contexts are addressed by HIP device index, and lvk_hip_device_count() is the number of indices worth trying -- the
  * highest gfx950 index + 1 (0 when there is no gfx950 device; never an error).  On the usual host every index below it is an MI355X; on a mixed
@@ -357,6 +357,26 @@ int  lvk_hip_stab_push_yuv420_host(lvk_hip_stab* stab, const void* h_y, int y_st
                                    int rows, int cols, uint64_t timestamp,
                                    void* oh_y, int oy_step, void* oh_u, int ou_step, void* oh_v, int ov_step, int o_rows,
                                    int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
+/* The host entry for ANY video format FrameIngest::Select accepts except Y800 (ABI 12): the contract of lvk_hip_stab_push_obs with h_planes / oh_planes
+ * in PINNED host memory -- what FrameIngest::upload_planes / download_planes do for every format alike (FrameIngest.cpp:415-474).  I420 / I40A / NV12
+ * are handed to lvk_hip_stab_push_yuv420_host unchanged (as lvk_hip_stab_push_obs hands them to lvk_hip_stab_push_yuv420).  Plane geometry per format
+ * as for lvk_hip_ingest_obs / lvk_hip_egress_obs: 4:2:2 planar chroma cols / 2 wide and rows high; packed 4:2:2 2 * cols bytes a row; AYUV 4 * cols;
+ * BGR3 3 * cols; RGBA / BGRA / BGRX rows * cols * 3 bytes of data[0] with steps[0] == 4 * cols, as the reference moves them; alpha planes are never
+ * touched.  The library schedules the transfers: one upload stream into staging planes sized for the format, planes that are contiguous in host
+ * memory as one copy, the luma plane of a planar format first (the tracker starts on it; packed formats travel whole); the output planes are written
+ * by the kernels THEMSELVES straight into the pinned host planes (the fused remap + egress sinks; BGR3 / RGBA / BGRA / BGRX, which have no fused sink:
+ * remap, then the egress into the host planes) -- there is no download route through device planes.  Input planes are consumed when the call returns;
+ * output planes are complete after lvk_hip_sync().  Shares the frame queue with lvk_hip_stab_push_obs, lvk_hip_stab_push_yuv420 and
+ * lvk_hip_stab_push_yuv420_host: the four may be mixed within a format class.  After a resize the next `frame_delay` outputs have the old size.
+ * REFUSED with LVK_HIP_ERR_ARG before anything changes (nothing queued or uploaded; the same push with good arguments then succeeds): everything
+ * lvk_hip_stab_push_obs refuses (a NULL plane, a short step, an odd width where the format subsamples, sizes <= 0, Y800 and unknown formats, output
+ * planes that cannot hold the DELAYED frame at its own size -- lvk_hip_stab_next_output --, a delayed frame of the other format class); an input or
+ * output plane that is pageable memory at either end of its extent; a push while frames announced through lvk_hip_stab_prefetch_yuv420_host are
+ * outstanding.  LOOK-AHEAD is out of scope for these formats: lvk_hip_stab_prefetch_yuv420_host announces 4:2:0 frames only. */
+int  lvk_hip_stab_push_obs_host(lvk_hip_stab* stab, int video_format,
+                                const void* const h_planes[3], const int steps[3], int rows, int cols, uint64_t timestamp,
+                                void* const oh_planes[3], const int o_steps[3], int o_rows,
+                                int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
 /* Look-ahead for streaming callers (the reader thread of VideoFilter::stream, Filters/VideoFilter.cpp:62-209, uploads ahead of the
  * filter thread): starts the upload of the planes that the NEXT lvk_hip_stab_push_yuv420_host call will push (same pointers), so that
  * the link carries frame n + 1 while frame n is tracked: announce frame n + 1, then push frame n.  Announced frames are pushed in the

@@ -17,7 +17,7 @@ static std::map<void*, lvk_hip_ctx*> g_block_owner;
 
 extern "C" {
 
-const char* lvk_hip_version(void) { return "lvk-hip 0.11 (gfx950, ABI 11)"; }
+const char* lvk_hip_version(void) { return "lvk-hip 0.12 (gfx950, ABI 12)"; }
 
 int lvk_hip_abi_version(void) { return LVK_HIP_ABI_VERSION; }
 

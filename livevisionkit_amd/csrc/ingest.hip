@@ -683,12 +683,13 @@ int lvk_launch_egress_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format
         return LVK_HIP_OK;
     case LVK_VIDEO_FORMAT_BGR3:
         LVK_HIP_REQUIRE(ctx, steps[0] >= 3 * cols && src_step >= 3 * cols);
-        LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(p0, (size_t)steps[0], src, (size_t)src_step, 3 * (size_t)cols, (size_t)rows, hipMemcpyDeviceToDevice, stream));
+        // (hipMemcpyDefault: the planes are the caller's -- device memory, or the pinned host planes of lvk_hip_stab_push_obs_host)
+        LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(p0, (size_t)steps[0], src, (size_t)src_step, 3 * (size_t)cols, (size_t)rows, hipMemcpyDefault, stream));
         return LVK_HIP_OK;
     case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX:
         // DirectIngest::to_obs: download_planes(src, dst) writes rows * cols * 3 bytes at data[0] (FrameIngest.cpp:751-753); the last quarter stays
         LVK_HIP_REQUIRE(ctx, steps[0] == 4 * cols && src_step >= 3 * cols);
-        LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(p0, 3 * (size_t)cols, src, (size_t)src_step, 3 * (size_t)cols, (size_t)rows, hipMemcpyDeviceToDevice, stream));
+        LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(p0, 3 * (size_t)cols, src, (size_t)src_step, 3 * (size_t)cols, (size_t)rows, hipMemcpyDefault, stream));
         return LVK_HIP_OK;
     default:
         return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_egress_obs: video format " + std::to_string(video_format) + " is not one FrameIngest::Select knows");

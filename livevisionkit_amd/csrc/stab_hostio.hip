@@ -1,14 +1,17 @@
-// Frames in HOST memory either side of the 4:2:0 path: staging planes, transfer streams, deferred downloads, upload look-ahead.
+// Frames in HOST memory either side of the filter (the 4:2:0 path and, through lvk_hip_stab_push_obs_host, every other OBS format): staging planes, transfer streams, deferred downloads, upload look-ahead.
 // Reference: FrameIngest::upload_planes / download_planes around to_ocl -> filter -> to_obs (Modules/OBS-Plugin/Interop/FrameIngest.cpp:415-474,
 // 494-602, VisionFilter.cpp:151-212).
 #include "stab_state.hpp"
 
 using namespace lvkstab;
 
-int lvk_hip_stab::ensure_hostio(int rows, int cols)
+int lvk_hip_stab::ensure_hostio(int rows, int cols, size_t in_bytes)
 {
     HostIO& h = hostio;
-    if (h.rows == rows && h.cols == cols && h.up) return LVK_HIP_OK;
+    const bool same = h.rows == rows && h.cols == cols && h.up;
+    if (same && h.in_bytes >= in_bytes) return LVK_HIP_OK;
+    // (an input slot only grows while the frame size stays: entries of different formats that alternate at one size do not rebuild the slots on every push)
+    const size_t in_keep = same ? h.in_bytes : 0;
     LVK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (remap_stream) LVK_HIP_CHECK(ctx, hipStreamSynchronize(remap_stream));
     // (LVK_HIP_HOST_SINK=copy: the last emitted frame of the old size may not have been handed to the copy engine yet -- it was reported as
@@ -16,7 +19,8 @@ int lvk_hip_stab::ensure_hostio(int rows, int cols)
     { const int frc = flush_download(true); if (frc != LVK_HIP_OK) return frc; }
     free_hostio();
     const size_t bytes = (size_t)rows * cols + 2 * (size_t)((rows + 1) / 2) * ((cols + 1) / 2);
-    for (auto& p : h.d_in) LVK_HIP_CHECK(ctx, hipMalloc(&p, bytes));
+    const size_t in_cap = std::max(bytes, std::max(in_bytes, in_keep));
+    for (auto& p : h.d_in) LVK_HIP_CHECK(ctx, hipMalloc(&p, in_cap));
     for (auto& p : h.d_out) LVK_HIP_CHECK(ctx, hipMalloc(&p, bytes));
     // The streams that exist are the streams that are used: every stream of the process is a queue the runtime maps onto its few hardware
     // queues, and a transfer stream that lands on the hardware queue of the caller's stream stalls the tracker's kernels behind its copies
@@ -38,7 +42,7 @@ int lvk_hip_stab::ensure_hostio(int rows, int cols)
         LVK_HIP_CHECK(ctx, hipEventCreateWithFlags(&h.down_done[i], hipEventDisableTiming));
         h.down_armed[i] = false;
     }
-    h.rows = rows; h.cols = cols; h.in_next = h.out_next = 0; h.last_down = -1; h.ahead.clear();
+    h.rows = rows; h.cols = cols; h.in_bytes = in_cap; h.in_next = h.out_next = 0; h.last_down = -1; h.ahead.clear();
     return LVK_HIP_OK;
 }
 
@@ -60,7 +64,7 @@ void lvk_hip_stab::free_hostio()
     for (auto& p : h.d_out) { if (p) (void)hipFree(p); p = nullptr; }
     for (auto* arr : {h.y_done, h.c_done}) for (int i = 0; i < HostIO::K_IN; i++) if (arr[i]) { (void)hipEventDestroy(arr[i]); arr[i] = nullptr; }
     for (auto* arr : {h.out_ready, h.down_done}) for (int i = 0; i < HostIO::K_OUT; i++) if (arr[i]) { (void)hipEventDestroy(arr[i]); arr[i] = nullptr; }
-    h.rows = h.cols = 0;
+    h.rows = h.cols = 0; h.in_bytes = 0;
 }
 
 // The uploads of one host frame into staging slot k, on the upload stream.
@@ -69,45 +73,83 @@ void lvk_hip_stab::free_hostio()
 //   * announced ahead (the link is the bottleneck, not this frame's latency): ONE copy when the planes are contiguous.  A copy engine
 //     that has to wait for anything but its own previous copy -- here: the event between the two copies -- is restarted by the
 //     runtime's signal handler 60-80 us late (timeline in profiles/r03_host_feed_timeline.txt): 341 us of link time per frame instead of 265.
-int lvk_hip_stab::host_upload(const void* h_y, int y_step, const void* h_u, int u_step, const void* h_v, int v_step, int nv12, int rows, int cols, int k, bool ahead)
+int lvk_hip_stab::host_upload(const HostPlane* pl, int n, int k, bool ahead)
 {
     HostIO& io = hostio;
-    const int crows = rows / 2, ccols = nv12 ? cols : cols / 2;
-    uint8_t* d_y = (uint8_t*)io.d_in[k];
-    uint8_t* d_u = d_y + (size_t)rows * cols;
-    uint8_t* d_v = nv12 ? d_u : d_u + (size_t)crows * ccols;
+    // the slot holds the planes tight, one after the other (Y | U | V, Y | UV, or the one plane of a packed format)
+    uint8_t* d[3] = {nullptr, nullptr, nullptr}; size_t total = 0;
+    for (int i = 0; i < n; i++) { d[i] = (uint8_t*)io.d_in[k] + total; total += (size_t)pl[i].width * pl[i].rows; }
+    LVK_HIP_REQUIRE(ctx, n >= 1 && n <= 3 && total <= io.in_bytes);
     // (the staging slot is free: the kernels that read it -- downscale, conversion -- were complete when the push that used it returned)
-    auto copy_plane = [&](void* dst, int dpitch, const void* src, int spitch, int width, int height, hipStream_t s) -> hipError_t {
-        if (spitch == width && dpitch == width) return hipMemcpyAsync(dst, src, (size_t)width * height, hipMemcpyHostToDevice, s);
-        return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyHostToDevice, s);
+    auto copy_plane = [&](void* dst, const HostPlane& h, hipStream_t s) -> hipError_t {
+        if (h.step == h.width) return hipMemcpyAsync(dst, h.p, (size_t)h.width * h.rows, hipMemcpyHostToDevice, s);
+        return hipMemcpy2DAsync(dst, h.width, h.p, h.step, h.width, h.rows, hipMemcpyHostToDevice, s);
     };
-    const bool contiguous = y_step == cols && u_step == ccols && (const uint8_t*)h_u == (const uint8_t*)h_y + (size_t)rows * cols &&
-                            (nv12 || (v_step == ccols && (const uint8_t*)h_v == (const uint8_t*)h_u + (size_t)crows * ccols));
-    if (ahead && contiguous)
+    // planes i and i + 1 lie back to back in host memory, as in the slot
+    auto follows = [&](int i) { return pl[i].step == pl[i].width && pl[i + 1].step == pl[i + 1].width &&
+                                       (const uint8_t*)pl[i + 1].p == (const uint8_t*)pl[i].p + (size_t)pl[i].width * pl[i].rows; };
+    bool contiguous = pl[0].step == pl[0].width;
+    for (int i = 0; i + 1 < n; i++) contiguous = contiguous && follows(i);
+    // ONE upload stream.  (hipMemcpyAsync blocks the host while an earlier copy of the same stream is still in flight, which two alternating
+    // streams would avoid, but a second stream costs more than that wait: see ensure_hostio; 3 140-3 190 against 2 700-2 850 frames/s.)
+    hipStream_t us = io.up;
+    if (n == 1 || (ahead && contiguous))
     {
-        const size_t bytes = (size_t)rows * cols + (size_t)(nv12 ? 1 : 2) * crows * ccols;
-        // ONE upload stream.  (hipMemcpyAsync blocks the host while an earlier copy of the same stream is still in flight, which two alternating
-        // streams would avoid, but a second stream costs more than that wait: see ensure_hostio; 3 140-3 190 against 2 700-2 850 frames/s.)
-        hipStream_t us = io.up;
-        LVK_HIP_CHECK(ctx, hipMemcpyAsync(d_y, h_y, bytes, hipMemcpyHostToDevice, us));
+        // a packed format's one plane, or a whole frame announced ahead: one event covers it
+        if (contiguous) LVK_HIP_CHECK(ctx, hipMemcpyAsync(d[0], pl[0].p, total, hipMemcpyHostToDevice, us));
+        else LVK_HIP_CHECK(ctx, copy_plane(d[0], pl[0], us));
         LVK_HIP_CHECK(ctx, hipEventRecord(io.c_done[k], us));
         io.y_is_c[k] = true;
         return LVK_HIP_OK;
     }
     io.y_is_c[k] = false;
-    hipStream_t cs = io.up;                                                          // luma and chroma of a frame pushed now: one stream, in order
-    LVK_HIP_CHECK(ctx, copy_plane(d_y, cols, h_y, y_step, cols, rows, io.up));
-    LVK_HIP_CHECK(ctx, hipEventRecord(io.y_done[k], io.up));
-    if (!nv12 && u_step == ccols && v_step == ccols && (const uint8_t*)h_v == (const uint8_t*)h_u + (size_t)crows * ccols)
+    LVK_HIP_CHECK(ctx, copy_plane(d[0], pl[0], us));                                 // luma and chroma of a frame pushed now: one stream, in order
+    LVK_HIP_CHECK(ctx, hipEventRecord(io.y_done[k], us));
+    if (n == 3 && follows(1))
     {
-        LVK_HIP_CHECK(ctx, hipMemcpyAsync(d_u, h_u, 2 * (size_t)crows * ccols, hipMemcpyHostToDevice, cs));      // U | V contiguous: one copy
+        LVK_HIP_CHECK(ctx, hipMemcpyAsync(d[1], pl[1].p, (size_t)pl[1].width * pl[1].rows + (size_t)pl[2].width * pl[2].rows, hipMemcpyHostToDevice, us));      // U | V contiguous: one copy
     }
-    else
+    else for (int i = 1; i < n; i++) LVK_HIP_CHECK(ctx, copy_plane(d[i], pl[i], us));
+    LVK_HIP_CHECK(ctx, hipEventRecord(io.c_done[k], us));
+    return LVK_HIP_OK;
+}
+
+// ---- what lvk_hip_stab_push_yuv420_host and lvk_hip_stab_push_obs_host share around the push they wrap
+// what a host entry hands to that push (events to wait for, the sink hints) never outlives the entry, whichever way it returns
+struct HostPushHooks
+{
+    lvk_hip_stab* s;
+    ~HostPushHooks() { s->remap_wait = nullptr; s->ingest_wait[0] = s->ingest_wait[1] = nullptr; s->host_free_running_hint = false; s->host_direct_now = false; }
+};
+
+int lvk_hip_stab::host_stage(const HostPlane* pl, int n, int* k)
+{
+    *k = hostio.in_next; hostio.in_next = (*k + 1) % HostIO::K_IN;
+    return host_upload(pl, n, *k, false);
+}
+
+// direct: the wrapped push's kernels store into the caller's pinned planes themselves
+int lvk_hip_stab::host_begin_push(int k, bool direct)
+{
+    HostIO& io = hostio;
+    LVK_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, io.y_is_c[k] ? io.c_done[k] : io.y_done[k], 0));           // the tracker needs the luma plane only
+    ingest_wait[0] = io.y_is_c[k] ? nullptr : io.y_done[k]; ingest_wait[1] = io.c_done[k];
+    host_free_running_hint = caller_free_running_now() ||
+                             (io.last_end.time_since_epoch().count() != 0 && std::chrono::steady_clock::now() - io.last_end < std::chrono::microseconds(15));
+    if (direct)
     {
-        LVK_HIP_CHECK(ctx, copy_plane(d_u, ccols, h_u, u_step, ccols, crows, cs));
-        if (!nv12) LVK_HIP_CHECK(ctx, copy_plane(d_v, ccols, h_v, v_step, ccols, crows, cs));
+        // a download of an earlier frame may still be writing the caller's (possibly the same) host planes: the kernel's stores follow it
+        const int rc = flush_download(true);
+        if (rc != LVK_HIP_OK) return rc;
+        if (io.last_down >= 0 && io.down_armed[io.last_down]) remap_wait = io.down_done[io.last_down];
     }
-    LVK_HIP_CHECK(ctx, hipEventRecord(io.c_done[k], cs));
+    return LVK_HIP_OK;
+}
+
+int lvk_hip_stab::host_end_push(int k)
+{
+    // "consumed on return": the conversion (which waited for both uploads) has finished in every mode by now; the event costs nothing then
+    LVK_HIP_CHECK(ctx, hipEventSynchronize(hostio.c_done[k]));
     return LVK_HIP_OK;
 }
 
@@ -179,13 +221,14 @@ int lvk_hip_stab_prefetch_yuv420_host(lvk_hip_stab* st, const void* h_y, int y_s
     LVK_HIP_REQUIRE(ctx, h_y && h_u && (nv12 || h_v) && rows > 0 && cols > 0 && rows % 2 == 0 && cols % 2 == 0);
     LVK_HIP_REQUIRE(ctx, y_step >= cols && u_step >= (nv12 ? cols : cols / 2) && (nv12 || v_step >= cols / 2));
     int rc;
-    if ((rc = st->require_pinned_planes(h_y, y_step, h_u, u_step, h_v, v_step, nv12, rows, cols, "lvk_hip_stab_prefetch_yuv420_host")) != LVK_HIP_OK) return rc;
+    HostPlane in[3]; const int n_in = lvk_hip_stab::planes420(h_y, y_step, h_u, u_step, h_v, v_step, nv12, rows, cols, in);
+    if ((rc = st->require_pinned_planes(in, n_in, "lvk_hip_stab_prefetch_yuv420_host")) != LVK_HIP_OK) return rc;
     if ((rc = st->ensure_hostio(rows, cols)) != LVK_HIP_OK) return rc;
     lvk_hip_stab::HostIO& io = st->hostio;
     // two staging slots: the frame being pushed and the one on the link -- at most two announced frames that have not been pushed yet
     LVK_HIP_REQUIRE(ctx, io.ahead.size() < (size_t)lvk_hip_stab::HostIO::K_IN);
     const int k = io.in_next; io.in_next = (k + 1) % lvk_hip_stab::HostIO::K_IN;
-    if ((rc = st->host_upload(h_y, y_step, h_u, u_step, h_v, v_step, nv12, rows, cols, k, true)) != LVK_HIP_OK) return rc;
+    if ((rc = st->host_upload(in, n_in, k, true)) != LVK_HIP_OK) return rc;
     io.ahead.push_back({k, {h_y, h_u, nv12 ? h_u : h_v}, rows, cols, nv12 ? 1 : 0});
     return LVK_HIP_OK;
 }
@@ -215,7 +258,8 @@ int lvk_hip_stab_push_yuv420_host(lvk_hip_stab* st, const void* h_y, int y_step,
     LVK_HIP_REQUIRE(ctx, h_y && h_u && (nv12 || h_v) && rows > 0 && cols > 0 && rows % 2 == 0 && cols % 2 == 0);
     LVK_HIP_REQUIRE(ctx, y_step >= cols && u_step >= (nv12 ? cols : cols / 2) && (nv12 || v_step >= cols / 2));
     int rc;
-    if ((rc = st->require_pinned_planes(h_y, y_step, h_u, u_step, h_v, v_step, nv12, rows, cols, "lvk_hip_stab_push_yuv420_host")) != LVK_HIP_OK) return rc;
+    HostPlane in[3]; const int n_in = lvk_hip_stab::planes420(h_y, y_step, h_u, u_step, h_v, v_step, nv12, rows, cols, in);
+    if ((rc = st->require_pinned_planes(in, n_in, "lvk_hip_stab_push_yuv420_host")) != LVK_HIP_OK) return rc;
     // the frame this push emits is the DELAYED one, at its own size (frames queued before a resize leave at the old size): the output planes are
     // checked -- pitch, rows, pinned over their whole extent -- against THAT geometry
     QueuedFrame due{};
@@ -227,7 +271,8 @@ int lvk_hip_stab_push_yuv420_host(lvk_hip_stab* st, const void* h_y, int y_step,
         if (!(oy_step >= ecols && ou_step >= (nv12 ? ecols : ecols / 2) && (nv12 || ov_step >= ecols / 2) && o_rows >= erows))
             return st->fail(LVK_HIP_ERR_ARG, "the output planes do not hold the frame this push emits: " + std::to_string(ecols) + " x " + std::to_string(erows) +
                                              " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
-        if ((rc = st->require_pinned_planes(oh_y, oy_step, oh_u, ou_step, oh_v, ov_step, nv12, erows, ecols, "lvk_hip_stab_push_yuv420_host (output)")) != LVK_HIP_OK) return rc;
+        HostPlane out[3]; const int n_out = lvk_hip_stab::planes420(oh_y, oy_step, oh_u, ou_step, oh_v, ov_step, nv12, erows, ecols, out);
+        if ((rc = st->require_pinned_planes(out, n_out, "lvk_hip_stab_push_yuv420_host (output)")) != LVK_HIP_OK) return rc;
     }
     if ((rc = st->ensure_hostio(rows, cols)) != LVK_HIP_OK) return rc;
     lvk_hip_stab::HostIO& io = st->hostio;
@@ -248,31 +293,22 @@ int lvk_hip_stab_push_yuv420_host(lvk_hip_stab* st, const void* h_y, int y_step,
     }
     else
     {
-        k = io.in_next; io.in_next = (k + 1) % lvk_hip_stab::HostIO::K_IN;
-        if ((rc = st->host_upload(h_y, y_step, h_u, u_step, h_v, v_step, nv12, rows, cols, k, false)) != LVK_HIP_OK) return rc;
+        if ((rc = st->host_stage(in, n_in, &k)) != LVK_HIP_OK) return rc;
     }
     uint8_t* d_y = (uint8_t*)io.d_in[k];
     uint8_t* d_u = d_y + (size_t)rows * cols;
     uint8_t* d_v = nv12 ? d_u : d_u + (size_t)crows * ccols;
     tr_mark(0);
-    // what this call hands to the push it wraps (events to wait for, the sink hints) never outlives it, whichever way it returns
-    struct ClearHooks
-    {
-        lvk_hip_stab* s;
-        ~ClearHooks() { s->remap_wait = nullptr; s->ingest_wait[0] = s->ingest_wait[1] = nullptr; s->host_free_running_hint = false; s->host_direct_now = false; }
-    } clear_hooks{st};
-    LVK_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, io.y_is_c[k] ? io.c_done[k] : io.y_done[k], 0));           // the tracker needs the luma plane only
-    st->ingest_wait[0] = io.y_is_c[k] ? nullptr : io.y_done[k]; st->ingest_wait[1] = io.c_done[k];
+    HostPushHooks clear_hooks{st};
 
     // where the output planes are written: by the remap kernel itself, straight into the pinned host planes (measured, 4K, free running:
     // 2 800 frames/s against 2 490 for remap -> device planes -> download, whose D2H copy the runtime performs with a blit KERNEL that
     // saturates the link's write queue and stalls every other kernel's memory traffic while it runs -- timelines under profiles/).
     // LVK_HIP_HOST_SINK=copy keeps the download route for comparison.
     const bool have_out = oh_y && oh_u && (nv12 || oh_v);
-    st->host_free_running_hint = st->caller_free_running_now() ||
-                                 (io.last_end.time_since_epoch().count() != 0 && std::chrono::steady_clock::now() - io.last_end < std::chrono::microseconds(15));
     // (a frame of an EARLIER size -- the staging planes of the download route have the new one -- always leaves through the kernel's own stores)
     const bool direct = have_out && (st->host_sink_mode != 2 || erows != rows || ecols != cols);
+    if ((rc = st->host_begin_push(k, direct)) != LVK_HIP_OK) return rc;
     const int j = io.out_next;
     uint8_t* o_y = nullptr; uint8_t* o_u = nullptr; uint8_t* o_v = nullptr;
     int oys = oy_step, ous = ou_step, ovs = ov_step;
@@ -283,20 +319,13 @@ int lvk_hip_stab_push_yuv420_host(lvk_hip_stab* st, const void* h_y, int y_step,
         if (io.pending.valid && io.pending.slot == j) { if ((rc = st->flush_download(true)) != LVK_HIP_OK) return rc; }
         if (io.down_armed[j]) st->remap_wait = io.down_done[j];                      // the download that last read this slot
     }
-    else if (have_out)
-    {
-        o_y = (uint8_t*)oh_y; o_u = (uint8_t*)oh_u; o_v = (uint8_t*)oh_v;
-        // a download of an earlier frame may still be writing the caller's (possibly the same) host planes: the kernel's stores follow it
-        if ((rc = st->flush_download(true)) != LVK_HIP_OK) return rc;
-        if (io.last_down >= 0 && io.down_armed[io.last_down]) st->remap_wait = io.down_done[io.last_down];
-    }
+    else if (have_out) { o_y = (uint8_t*)oh_y; o_u = (uint8_t*)oh_u; o_v = (uint8_t*)oh_v; }
     int prod = 0;
     tr_mark(1);
     st->host_direct_now = direct;
     rc = lvk_hip_stab_push_yuv420(st, d_y, cols, d_u, ccols, d_v, ccols, nv12, rows, cols, timestamp, o_y, oys, o_u, ous, o_v, ovs, direct ? o_rows : rows, &prod, out_timestamp, emitted);
     tr_mark(2);
-    // "consumed on return": the conversion (which waited for both uploads) has finished in every mode by now; the event costs nothing then
-    LVK_HIP_CHECK(ctx, hipEventSynchronize(io.c_done[k]));
+    { const int erc = st->host_end_push(k); if (erc != LVK_HIP_OK) return erc; }
     tr_mark(3);
     if (rc != LVK_HIP_OK) return rc;
     if ((rc = st->flush_download(false)) != LVK_HIP_OK) return rc;                  // the previous frame's remap has usually finished by now
@@ -312,6 +341,80 @@ int lvk_hip_stab_push_yuv420_host(lvk_hip_stab* st, const void* h_y, int y_step,
     }
     if (produced) *produced = prod;
     tr_mark(4); st->host_trace_n++;
+    io.last_end = std::chrono::steady_clock::now();
+    return LVK_HIP_OK;
+}
+
+// The host entry for EVERY OBS video format FrameIngest::Select accepts (except Y800): lvk_hip_stab_push_obs with the planes in pinned host memory --
+// what FrameIngest::upload_planes / download_planes do for every format alike (Modules/OBS-Plugin/Interop/FrameIngest.cpp:415-474).  I420 / I40A / NV12
+// are lvk_hip_stab_push_yuv420_host's.  The other formats share its machinery:
+//   in:  the planes go through the one upload stream into a staging slot sized for the format; planar formats luma first with its own event (the tracker
+//        starts on it), packed formats one copy and one event; planes contiguous in host memory travel as one copy;
+//   out: the fused remap + egress sinks (remap_obs.hip) store into the caller's pinned planes themselves; the formats without a fused sink (BGR3, RGBA,
+//        BGRA, BGRX) take remap -> packed buffer -> egress, whose destination is the host planes.  No download route through device planes.
+// Refused before anything changes: everything lvk_hip_stab_push_obs refuses, pageable planes, and a push while 4:2:0 look-ahead frames are outstanding.
+int lvk_hip_stab_push_obs_host(lvk_hip_stab* st, int video_format, const void* const h_planes[3], const int steps[3], int rows, int cols, uint64_t timestamp,
+                               void* const oh_planes[3], const int o_steps[3], int o_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted)
+{
+    if (!st) return LVK_HIP_ERR_ARG;
+    if (produced) *produced = 0;
+    const int vf = video_format;
+    if (vf == LVK_VIDEO_FORMAT_I420 || vf == LVK_VIDEO_FORMAT_I40A || vf == LVK_VIDEO_FORMAT_NV12)
+    {
+        const int nv12 = vf == LVK_VIDEO_FORMAT_NV12 ? 1 : 0;
+        if (!h_planes || !steps) return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs_host: no input planes");
+        void* const none[3] = {nullptr, nullptr, nullptr}; const int zero[3] = {0, 0, 0};
+        void* const* op = oh_planes && o_steps ? oh_planes : none; const int* os = oh_planes && o_steps ? o_steps : zero;
+        return lvk_hip_stab_push_yuv420_host(st, h_planes[0], steps[0], h_planes[1], steps[1], nv12 ? h_planes[1] : h_planes[2], nv12 ? steps[1] : steps[2], nv12,
+                                             rows, cols, timestamp, op[0], os[0], op[1], os[1], nv12 ? op[1] : op[2], nv12 ? os[1] : os[2], o_rows,
+                                             produced, out_timestamp, emitted);
+    }
+    lvk_device_guard device_guard(st->ctx);
+    lvk_hip_ctx* ctx = st->ctx;
+    int rc, frame_format = 0;
+    QueuedFrame due{}; bool will_emit = false;
+    if ((rc = lvk_stab_check_in_planes(st, vf, h_planes, steps, rows, cols, &frame_format)) != LVK_HIP_OK) return rc;
+    if ((rc = lvk_stab_check_due(st, vf, frame_format, rows, cols, timestamp, oh_planes, o_steps, o_rows, &due, &will_emit)) != LVK_HIP_OK) return rc;
+    lvk_hip_stab::HostIO& io = st->hostio;
+    if (!io.ahead.empty())
+        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs_host: frames announced through lvk_hip_stab_prefetch_yuv420_host have not been pushed yet -- push them "
+                                         "(lvk_hip_stab_push_yuv420_host) or lvk_hip_stab_prefetch_cancel() first; nothing was queued");
+    HostPlane in[3]; const int n_in = host_planes_of(vf, h_planes, steps, rows, cols, in);
+    LVK_HIP_REQUIRE(ctx, n_in > 0);
+    if ((rc = st->require_pinned_planes(in, n_in, "lvk_hip_stab_push_obs_host")) != LVK_HIP_OK) return rc;
+    // the output planes are checked -- pinned over their whole extent -- against the geometry of the frame this push emits (the DELAYED one, which
+    // lvk_stab_check_due has found them large enough for); planes given to a push that emits nothing are not touched, and are held to the incoming
+    // frame's geometry when they have it: pageable memory is refused whenever it is seen
+    const bool rgbx = vf == LVK_VIDEO_FORMAT_RGBA || vf == LVK_VIDEO_FORMAT_BGRA || vf == LVK_VIDEO_FORMAT_BGRX;
+    const int erows = will_emit ? due.rows : rows, ecols = will_emit ? due.cols : cols;
+    if (oh_planes && o_steps && oh_planes[0] && o_rows >= erows)
+    {
+        HostPlane out[3]; const int n_out = host_planes_of(vf, oh_planes, o_steps, erows, ecols, out);
+        bool whole = true;
+        for (int i = 0; i < n_out; i++) whole = whole && out[i].p && out[i].step >= out[i].width;
+        // (DirectIngest's 4-byte formats are a tight byte stream by definition: the egress refuses another pitch -- here, before the frame is queued)
+        if (rgbx && o_steps[0] != 4 * ecols) { if (will_emit) return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs_host: RGBA / BGRA / BGRX output planes are tight (o_steps[0] == 4 * cols of the emitted frame); nothing was queued"); whole = false; }
+        if (whole && (rc = st->require_pinned_planes(out, n_out, "lvk_hip_stab_push_obs_host (output)")) != LVK_HIP_OK) return rc;
+    }
+    size_t in_bytes = 0;
+    for (int i = 0; i < n_in; i++) in_bytes += (size_t)in[i].width * in[i].rows;
+    if ((rc = st->ensure_hostio(rows, cols, in_bytes)) != LVK_HIP_OK) return rc;
+    if ((rc = st->flush_download(false)) != LVK_HIP_OK) return rc;
+    int k = 0;
+    if ((rc = st->host_stage(in, n_in, &k)) != LVK_HIP_OK) return rc;
+    // the staged planes, tight (the 4-byte formats: the 3 * cols bytes a row that were moved, under the pitch DirectIngest declares)
+    const void* d_planes[3] = {nullptr, nullptr, nullptr}; int d_steps[3] = {0, 0, 0};
+    { size_t off = 0; for (int i = 0; i < n_in; i++) { d_planes[i] = (const uint8_t*)io.d_in[k] + off; d_steps[i] = rgbx ? 4 * cols : in[i].width; off += (size_t)in[i].width * in[i].rows; } }
+    HostPushHooks clear_hooks{st};
+    // every emitted frame leaves through stores into the host planes; the remap itself crosses the link only where its sink is fused
+    if ((rc = st->host_begin_push(k, will_emit)) != LVK_HIP_OK) return rc;
+    st->host_direct_now = will_emit && lvk_remap_obs_fusable(vf);
+    int prod = 0;
+    rc = lvk_hip_stab_push_obs(st, vf, d_planes, d_steps, rows, cols, timestamp, oh_planes, o_steps, o_rows, &prod, out_timestamp, emitted);
+    { const int erc = st->host_end_push(k); if (erc != LVK_HIP_OK) return erc; }
+    if (rc != LVK_HIP_OK) return rc;
+    if ((rc = st->flush_download(false)) != LVK_HIP_OK) return rc;
+    if (produced) *produced = prod;
     io.last_end = std::chrono::steady_clock::now();
     return LVK_HIP_OK;
 }

@@ -78,12 +78,35 @@ struct QueuedFrame { const void* d_ptr; int step, rows, cols; uint64_t ts; int f
 // remap (lvk_launch_warpmesh_apply_obs): planes / steps as FrameIngest::to_obs writes them, their geometry checked by lvk_stab_push_planes
 struct OutPlanes420 { void* y; int y_step; void* u; int u_step; void* v; int v_step; int nv12; bool used; int rows_cap = 0; int vf = 0; void* p[3] = {nullptr, nullptr, nullptr}; int s[3] = {0, 0, 0}; };
 
+// one plane of a frame in host memory, as the host entry points move it: `rows` rows of `width` BYTES, `step` bytes apart
+struct HostPlane { const void* p; int step, width, rows; };
+
+// The planes FrameIngest moves for one frame of an OBS video format (lvk_hip_ingest_obs / lvk_hip_egress_obs; the alpha planes of I40A / I42A / YUVA stay
+// where they are).  RGBA / BGRA / BGRX: rows * cols * 3 bytes of the tight 4-byte pixels, as DirectIngest moves them (FrameIngest.cpp:743-753).
+// Returns the number of planes (0: a format without planes here), planes[i] / steps[i] not yet validated.
+inline int host_planes_of(int vf, const void* const planes[3], const int steps[3], int rows, int cols, HostPlane out[3])
+{
+    auto set = [&](int i, int w, int r, bool tight = false) { out[i] = HostPlane{planes[i], tight ? w : steps[i], w, r}; };
+    switch (vf)
+    {
+    case LVK_VIDEO_FORMAT_I420: case LVK_VIDEO_FORMAT_I40A: set(0, cols, rows); set(1, cols / 2, rows / 2); set(2, cols / 2, rows / 2); return 3;
+    case LVK_VIDEO_FORMAT_NV12: set(0, cols, rows); set(1, cols, rows / 2); return 2;
+    case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A: set(0, cols, rows); set(1, cols / 2, rows); set(2, cols / 2, rows); return 3;
+    case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA: set(0, cols, rows); set(1, cols, rows); set(2, cols, rows); return 3;
+    case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: case LVK_VIDEO_FORMAT_UYVY: set(0, 2 * cols, rows); return 1;
+    case LVK_VIDEO_FORMAT_AYUV: set(0, 4 * cols, rows); return 1;
+    case LVK_VIDEO_FORMAT_BGR3: set(0, 3 * cols, rows); return 1;
+    case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX: set(0, 3 * cols, rows, true); return 1;
+    default: return 0;
+    }
+}
+
 } // namespace lvkstab
 
 struct lvk_hip_stab
 {
     using Feature = lvkstab::Feature; using WarpMeshF = lvkstab::WarpMeshF; using QueuedFrame = lvkstab::QueuedFrame; using HostTrace = lvkstab::HostTrace;
-    using OutPlanes420 = lvkstab::OutPlanes420;
+    using OutPlanes420 = lvkstab::OutPlanes420; using HostPlane = lvkstab::HostPlane;
     lvk_hip_ctx* ctx = nullptr;
     lvk_stab_settings s{};
     bool configured = false;
@@ -264,6 +287,7 @@ struct lvk_hip_stab
         hipStream_t up = nullptr, down = nullptr, down2 = nullptr;
         struct Pending { bool valid = false; int slot = 0; void* y; void* u; void* v; int ys, us, vs, nv12; } pending;      // a download not yet handed to the copy engine
         int rows = 0, cols = 0;
+        size_t in_bytes = 0;                                    // capacity of one input staging slot (the 4:2:0 frame, or a larger format's planes)
         void* d_in[K_IN] = {nullptr, nullptr}; void* d_out[K_OUT] = {nullptr, nullptr, nullptr};      // contiguous planes: Y | U | V  (or Y | UV)
         hipEvent_t y_done[K_IN] = {}, c_done[K_IN] = {}, out_ready[K_OUT] = {}, down_done[K_OUT] = {};
         bool down_armed[K_OUT] = {false, false, false};
@@ -279,7 +303,7 @@ struct lvk_hip_stab
     bool host_direct_now = false;                        // the push being wrapped writes its output planes straight into host memory
     hipEvent_t ingest_wait[2] = {nullptr, nullptr};      // events the newest frame's 4:2:0 conversion waits for (the plane uploads), or nullptr
     hipEvent_t remap_wait = nullptr;                     // event the next remap waits for (the download that last read its output planes)
-    int ensure_hostio(int rows, int cols);
+    int ensure_hostio(int rows, int cols, size_t in_bytes = 0);      // in_bytes: what one input staging slot must hold when that is more than the 4:2:0 frame
     // The host entry points hand these pointers to copy engines and (output planes) to a kernel: pageable memory there is a GPU fault, not an
     // error code.  Looked up on EVERY call (hipPointerGetAttributes: ~1 us) -- an address that was pinned once may be pageable memory the next
     // time it is seen (hipHostFree / hipHostUnregister, then malloc) -- and at BOTH ends of the byte range, so that a plane that runs past
@@ -298,18 +322,28 @@ struct lvk_hip_stab
         }
         return LVK_HIP_OK;
     }
-    // the planes of one 4:2:0 frame: one range when they are contiguous (the OBS layout), else plane by plane
-    int require_pinned_planes(const void* y, int y_step, const void* u, int u_step, const void* v, int v_step, int nv12, int rows, int cols, const char* what)
+    // the planes of one frame: one range when they are contiguous (the OBS layout), else plane by plane
+    int require_pinned_planes(const HostPlane* pl, int n, const char* what)
     {
-        if (!y) return LVK_HIP_OK;
-        const int crows = rows / 2, ccols = nv12 ? cols : cols / 2;
-        const size_t yb = (size_t)y_step * (rows - 1) + cols, ub = (size_t)u_step * (crows - 1) + ccols, vb = nv12 ? 0 : (size_t)v_step * (crows - 1) + ccols;
-        const uint8_t* ye = (const uint8_t*)y + yb; const uint8_t* ue = (const uint8_t*)u + ub;
-        if (y_step == cols && u_step == ccols && (const uint8_t*)u == ye && (nv12 || (v_step == ccols && (const uint8_t*)v == ue)))
-            return require_pinned(y, yb + ub + vb, what);
-        int rc;
-        if ((rc = require_pinned(y, yb, what)) != LVK_HIP_OK || (rc = require_pinned(u, ub, what)) != LVK_HIP_OK) return rc;
-        return nv12 ? LVK_HIP_OK : require_pinned(v, vb, what);
+        if (n <= 0 || !pl[0].p) return LVK_HIP_OK;
+        auto extent = [](const HostPlane& h) { return (size_t)h.step * (h.rows - 1) + h.width; };
+        bool contiguous = true; size_t total = 0;
+        for (int i = 0; i < n; i++)
+        {
+            contiguous = contiguous && pl[i].step == pl[i].width && (const uint8_t*)pl[i].p == (const uint8_t*)pl[0].p + total;
+            total += extent(pl[i]);
+        }
+        if (contiguous) return require_pinned(pl[0].p, total, what);
+        for (int i = 0; i < n; i++) { const int rc = require_pinned(pl[i].p, extent(pl[i]), what); if (rc != LVK_HIP_OK) return rc; }
+        return LVK_HIP_OK;
+    }
+    // (the 4:2:0 entries' argument list as such planes; returns their number)
+    static int planes420(const void* y, int y_step, const void* u, int u_step, const void* v, int v_step, int nv12, int rows, int cols, HostPlane out[3])
+    {
+        out[0] = HostPlane{y, y_step, cols, rows};
+        out[1] = HostPlane{u, u_step, nv12 ? cols : cols / 2, rows / 2};
+        out[2] = HostPlane{v, v_step, cols / 2, rows / 2};
+        return nv12 ? 2 : 3;
     }
     int host_stream(hipStream_t& s)                          // a transfer stream, created on first use; lvk_hip_sync() covers it
     {
@@ -340,7 +374,11 @@ struct lvk_hip_stab
         return LVK_HIP_OK;
     }
     int launch_build_ahead(DevicePyramid& P, int cur_w, int cur_h);      // stab_lookahead.hip
-    int host_upload(const void* h_y, int y_step, const void* h_u, int u_step, const void* h_v, int v_step, int nv12, int rows, int cols, int k, bool ahead);
+    int host_upload(const HostPlane* pl, int n, int k, bool ahead);
+    // what the two host entries share around the push they wrap (stab_hostio.hip)
+    int host_stage(const HostPlane* pl, int n, int* k);      // the next staging slot and the uploads into it
+    int host_begin_push(int k, bool direct);                 // the hooks of the wrapped push: upload events, the caller's pace, the direct sink's ordering
+    int host_end_push(int k);                                // "consumed on return"
     void free_hostio();
     bool caller_free_running_now();
     double host_trace_acc[6] = {0, 0, 0, 0, 0, 0}; long host_trace_n = 0;      // LVK_HIP_HOST_TRACE: us inside lvk_hip_stab_push_yuv420_host, by phase
@@ -360,6 +398,11 @@ struct lvk_hip_stab
     int ensure_pool(int rows, int cols);
     void free_pool();
 };
+
+// What lvk_hip_stab_push_obs refuses before anything changes (stabilizer.hip), for the host entry that wraps it
+int lvk_stab_check_in_planes(lvk_hip_stab* st, int vf, const void* const in_planes[3], const int in_steps[3], int rows, int cols, int* frame_format);
+int lvk_stab_check_due(lvk_hip_stab* st, int vf, int frame_format, int rows, int cols, uint64_t timestamp, void* const op[3], const int os[3], int o_rows,
+                       lvkstab::QueuedFrame* due, bool* will_emit);
 
 // StabilizationFilter::filter (stabilizer.hip); the entry points of the other units wrap it
 int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows, int cols, uint64_t timestamp, int format,

@@ -658,6 +658,61 @@ void lvk_hip_stab::free_pool()
     pool_rows = pool_cols = 0;
 }
 
+static const char* lvk_frame_format_name(int f)
+{
+    switch (f)
+    {
+    case LVK_FORMAT_BGR: return "BGR"; case LVK_FORMAT_BGRA: return "BGRA"; case LVK_FORMAT_RGB: return "RGB"; case LVK_FORMAT_RGBA: return "RGBA";
+    case LVK_FORMAT_YUV: return "YUV"; case LVK_FORMAT_GRAY: return "GRAY"; default: return "?";
+    }
+}
+
+// What lvk_stab_push_planes refuses before anything changes, as two checks that touch nothing -- shared with lvk_hip_stab_push_obs_host (stab_hostio.hip),
+// which must refuse the same pushes BEFORE it uploads a plane.  1: the planes FrameIngest::to_ocl would read; *frame_format = the VideoFrame format of `vf`.
+int lvk_stab_check_in_planes(lvk_hip_stab* st, int vf, const void* const in_planes[3], const int in_steps[3], int rows, int cols, int* frame_format)
+{
+    lvk_hip_ctx* ctx = st->ctx;
+    *frame_format = lvk_hip_obs_frame_format(vf);
+    if (*frame_format < 0 || *frame_format == LVK_FORMAT_GRAY || !in_planes || !in_steps || !in_planes[0])
+        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs: video format " + std::to_string(vf) + " has no three-channel frame the filter could take (FrameIngest::Select, lvk::remap: CV_8UC3)");
+    // what the conversion will read (planes, pitches, the parity of the size) is checked HERE, before the pool, the tracker or the queue changes: in overlap
+    // mode the conversion itself is launched only after track() and the queue have moved, and a refusal there left an unconverted slot queued
+    return lvk_ingest_obs_check(ctx, vf, in_planes, in_steps, rows, cols);
+}
+
+// 2: the frame this push would emit -- *will_emit, *due = the DELAYED frame -- against this push's format class and its output planes.
+int lvk_stab_check_due(lvk_hip_stab* st, int vf, int frame_format, int rows, int cols, uint64_t timestamp, void* const op[3], const int os[3], int o_rows,
+                       lvkstab::QueuedFrame* due_out, bool* will_emit_out)
+{
+    const bool is420 = vf == LVK_VIDEO_FORMAT_I420 || vf == LVK_VIDEO_FORMAT_I40A || vf == LVK_VIDEO_FORMAT_NV12;
+    if (!st->queue.empty() && st->queue_kind == 1) return st->fail(LVK_HIP_ERR_ARG, "borrowed frames of lvk_hip_stab_push are still queued: restart() before switching to lvk_hip_stab_push_yuv420");
+    QueuedFrame due{};
+    const bool will_emit = st->next_output(QueuedFrame{nullptr, 3 * cols, rows, cols, timestamp, frame_format}, &due);
+    // The emitted frame leaves in THIS push's video format.  A delayed frame of the other format class (BGR / RGB against YUV) would be run through the
+    // wrong EASU program and written as the wrong bytes: the reference converts it into its own OBS frame (OBSFrame::to_obs_frame, viewAsFormat), which a
+    // one-format-per-push call cannot do -- refused, before anything changes (declared deviation, include/lvk_hip.h; restart() recovers).
+    if (will_emit && due.format != frame_format)
+        return st->fail(LVK_HIP_ERR_ARG, std::string("the frame this push emits was queued as ") + lvk_frame_format_name(due.format) + " and this push's planes are " +
+                                             lvk_frame_format_name(frame_format) + " (video format " + std::to_string(vf) + "): the emitted frame is not converted between BGR / RGB and YUV -- "
+                                             "restart() before switching; nothing was queued");
+    if (!is420 && will_emit)
+    {
+        // the planes of the frame this push emits (the DELAYED one, at its own size) must hold it: refused before anything changes, like the 4:2:0 planes
+        const int packed = (vf == LVK_VIDEO_FORMAT_YUY2 || vf == LVK_VIDEO_FORMAT_YVYU || vf == LVK_VIDEO_FORMAT_UYVY) ? 2 :
+                           (vf == LVK_VIDEO_FORMAT_AYUV || vf == LVK_VIDEO_FORMAT_RGBA || vf == LVK_VIDEO_FORMAT_BGRA || vf == LVK_VIDEO_FORMAT_BGRX) ? 4 :
+                           vf == LVK_VIDEO_FORMAT_BGR3 ? 3 : 0;
+        const int cw = (vf == LVK_VIDEO_FORMAT_I422 || vf == LVK_VIDEO_FORMAT_I42A) ? due.cols / 2 : due.cols;
+        const bool fits = op && os && op[0] && o_rows >= due.rows &&
+                          (packed ? os[0] >= packed * due.cols : (op[1] && op[2] && os[0] >= due.cols && os[1] >= cw && os[2] >= cw));
+        if (!fits)
+            return st->fail(LVK_HIP_ERR_ARG, "the output planes do not hold the frame this push emits: " + std::to_string(due.cols) + " x " + std::to_string(due.rows) +
+                                                 " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
+    }
+    if (due_out) *due_out = due;
+    if (will_emit_out) *will_emit_out = will_emit;
+    return LVK_HIP_OK;
+}
+
 extern "C" {
 
 int lvk_hip_stab_next_output(const lvk_hip_stab* st, int rows, int cols, int format, lvk_frame_info* out)
@@ -691,15 +746,6 @@ int lvk_hip_stab_push(lvk_hip_stab* st, const void* d_frame, int step, int rows,
     return rc;
 }
 
-static const char* lvk_frame_format_name(int f)
-{
-    switch (f)
-    {
-    case LVK_FORMAT_BGR: return "BGR"; case LVK_FORMAT_BGRA: return "BGRA"; case LVK_FORMAT_RGB: return "RGB"; case LVK_FORMAT_RGBA: return "RGBA";
-    case LVK_FORMAT_YUV: return "YUV"; case LVK_FORMAT_GRAY: return "GRAY"; default: return "?";
-    }
-}
-
 // The OBS asynchronous path in one call: I4XXIngest / NV12Ingest::to_ocl -> StabilizationFilter::filter -> ::to_obs
 // (Modules/OBS-Plugin/Interop/VisionFilter.cpp:151-212, FrameIngest.cpp:494-602).  Planar (or NV12) 4:2:0 in, 4:2:0 out;
 // the packed 8UC3 frames the filter works on live in an internal pool (predictive_samples + 4 frames).  The input planes
@@ -715,12 +761,8 @@ static int lvk_stab_push_planes(lvk_hip_stab* st, int vf, const void* const in_p
     lvk_hip_ctx* ctx = st->ctx;
     const bool is420 = vf == LVK_VIDEO_FORMAT_I420 || vf == LVK_VIDEO_FORMAT_I40A || vf == LVK_VIDEO_FORMAT_NV12;
     const int nv12 = vf == LVK_VIDEO_FORMAT_NV12 ? 1 : 0;
-    const int frame_format = lvk_hip_obs_frame_format(vf);
-    if (frame_format < 0 || frame_format == LVK_FORMAT_GRAY || !in_planes || !in_steps || !in_planes[0])
-        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs: video format " + std::to_string(vf) + " has no three-channel frame the filter could take (FrameIngest::Select, lvk::remap: CV_8UC3)");
-    // what the conversion will read (planes, pitches, the parity of the size) is checked HERE, before the pool, the tracker or the queue changes: in overlap
-    // mode the conversion itself is launched only after track() and the queue have moved, and a refusal there left an unconverted slot queued
-    { const int rc0 = lvk_ingest_obs_check(ctx, vf, in_planes, in_steps, rows, cols); if (rc0 != LVK_HIP_OK) return rc0; }
+    int frame_format = 0;
+    { const int rc0 = lvk_stab_check_in_planes(st, vf, in_planes, in_steps, rows, cols, &frame_format); if (rc0 != LVK_HIP_OK) return rc0; }
     const std::array<const void*, 3> ip{in_planes[0], in_planes[1], in_planes[2]};
     const std::array<int, 3> is_{in_steps[0], in_steps[1], in_steps[2]};
     std::array<void*, 3> op{nullptr, nullptr, nullptr}; std::array<int, 3> os{0, 0, 0};
@@ -741,29 +783,7 @@ static int lvk_stab_push_planes(lvk_hip_stab* st, int vf, const void* const in_p
     struct AnnouncementEnds { lvk_hip_stab* s; ~AnnouncementEnds() { s->ahead_announced = lvk_hip_stab::LumaAhead(); } } announcement_ends{st};
     if (produced) *produced = 0;
     if (st->queue.empty()) st->queue_kind = 0;
-    if (st->queue_kind == 1) return st->fail(LVK_HIP_ERR_ARG, "borrowed frames of lvk_hip_stab_push are still queued: restart() before switching to lvk_hip_stab_push_yuv420");
-    QueuedFrame due{};
-    const bool will_emit = st->next_output(QueuedFrame{nullptr, 3 * cols, rows, cols, timestamp, frame_format}, &due);
-    // The emitted frame leaves in THIS push's video format.  A delayed frame of the other format class (BGR / RGB against YUV) would be run through the
-    // wrong EASU program and written as the wrong bytes: the reference converts it into its own OBS frame (OBSFrame::to_obs_frame, viewAsFormat), which a
-    // one-format-per-push call cannot do -- refused, before anything changes (declared deviation, include/lvk_hip.h; restart() recovers).
-    if (will_emit && due.format != frame_format)
-        return st->fail(LVK_HIP_ERR_ARG, std::string("the frame this push emits was queued as ") + lvk_frame_format_name(due.format) + " and this push's planes are " +
-                                             lvk_frame_format_name(frame_format) + " (video format " + std::to_string(vf) + "): the emitted frame is not converted between BGR / RGB and YUV -- "
-                                             "restart() before switching; nothing was queued");
-    if (!is420 && will_emit)
-    {
-        // the planes of the frame this push emits (the DELAYED one, at its own size) must hold it: refused before anything changes, like the 4:2:0 planes
-        const int packed = (vf == LVK_VIDEO_FORMAT_YUY2 || vf == LVK_VIDEO_FORMAT_YVYU || vf == LVK_VIDEO_FORMAT_UYVY) ? 2 :
-                           (vf == LVK_VIDEO_FORMAT_AYUV || vf == LVK_VIDEO_FORMAT_RGBA || vf == LVK_VIDEO_FORMAT_BGRA || vf == LVK_VIDEO_FORMAT_BGRX) ? 4 :
-                           vf == LVK_VIDEO_FORMAT_BGR3 ? 3 : 0;
-        const int cw = (vf == LVK_VIDEO_FORMAT_I422 || vf == LVK_VIDEO_FORMAT_I42A) ? due.cols / 2 : due.cols;
-        const bool fits = op[0] && o_rows >= due.rows &&
-                          (packed ? os[0] >= packed * due.cols : (op[1] && op[2] && os[0] >= due.cols && os[1] >= cw && os[2] >= cw));
-        if (!fits)
-            return st->fail(LVK_HIP_ERR_ARG, "the output planes do not hold the frame this push emits: " + std::to_string(due.cols) + " x " + std::to_string(due.rows) +
-                                                 " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
-    }
+    { const int rc0 = lvk_stab_check_due(st, vf, frame_format, rows, cols, timestamp, op.data(), os.data(), o_rows, nullptr, nullptr); if (rc0 != LVK_HIP_OK) return rc0; }
     st->queue_kind = 2;
     int rc = st->ensure_pool(rows, cols);
     if (rc != LVK_HIP_OK) return rc;

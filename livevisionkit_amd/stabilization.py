@@ -336,6 +336,54 @@ class StabilizationFilter:
             self.ctx._check(rc)
         return (dst["planes"], ots.value) if produced.value else (None, None)
 
+    # ---- host-resident frames of any OBS video format (lvk_hip_stab_push_obs_host)
+    @staticmethod
+    def obs_plane_shapes(fmt, rows, cols):
+        """Shapes of the planes FrameIngest moves for one rows x cols frame of `fmt` (the alpha planes of I40A / I42A / YUVA are never touched)."""
+        if fmt in ("I420", "I40A"): return [(rows, cols), (rows // 2, cols // 2), (rows // 2, cols // 2)]
+        if fmt == "NV12": return [(rows, cols), (rows // 2, cols // 2, 2)]
+        if fmt in ("I422", "I42A"): return [(rows, cols), (rows, cols // 2), (rows, cols // 2)]
+        if fmt in ("I444", "YUVA"): return [(rows, cols)] * 3
+        if fmt in ("YUY2", "YVYU", "UYVY"): return [(rows, cols, 2)]
+        if fmt in ("AYUV", "RGBA", "BGRA", "BGRX"): return [(rows, cols, 4)]
+        if fmt == "BGR3": return [(rows, cols, 3)]
+        raise ValueError("no host planes for video format %r" % (fmt,))
+
+    def host_planes_obs(self, fmt, rows, cols, pitch_extra=0):
+        """One pinned frame of `fmt` in one lvk_hip_host_malloc block: numpy views of the shapes of obs_plane_shapes, one after the other (the OBS
+        layout: contiguous when pitch_extra == 0), every row `pitch_extra` bytes longer than its pixels otherwise."""
+        shapes = self.obs_plane_shapes(fmt, rows, cols)
+        rowb = [sh[1] * (sh[2] if len(sh) == 3 else 1) for sh in shapes]
+        sizes = [sh[0] * (rb + pitch_extra) for sh, rb in zip(shapes, rowb)]
+        n = sum(sizes)
+        p = _c.c_void_p()
+        self.ctx._check(self.lib.lvk_hip_host_malloc(self.ctx.handle, n, _c.byref(p)))
+        self._host_blocks = getattr(self, "_host_blocks", []); self._host_blocks.append(p)
+        buf = np.ctypeslib.as_array((_c.c_uint8 * n).from_address(p.value))
+        planes, off = [], 0
+        for sh, rb, size in zip(shapes, rowb, sizes):
+            planes.append(buf[off:off + size].reshape(sh[0], rb + pitch_extra)[:, :rb].reshape(sh) if pitch_extra == 0 else
+                          np.lib.stride_tricks.as_strided(buf[off:off + size], sh, (rb + pitch_extra,) + ((sh[2], 1) if len(sh) == 3 else (1,))))
+            off += size
+        return tuple(planes)
+
+    def prepare_obs_host(self, fmt, planes):
+        """ctypes argument block of one OBS frame's host planes (numpy uint8 arrays in pinned memory) for apply_obs_host_prepared."""
+        ptrs = (_c.c_void_p * 3)(*[p.ctypes.data for p in planes] + [None] * (3 - len(planes)))
+        steps = (_c.c_int * 3)(*[p.strides[0] for p in planes] + [0] * (3 - len(planes)))
+        return {"vf": _c.c_int(self.ctx.VIDEO_FORMATS[fmt]), "ptrs": ptrs, "steps": steps, "rows": _c.c_int(planes[0].shape[0]),
+                "cols": _c.c_int(planes[0].shape[1]), "planes": planes}
+
+    def apply_obs_host_prepared(self, src, timestamp, dst):
+        """lvk_hip_stab_push_obs_host: pinned host planes of any OBS format in, pinned host planes out (complete after Context.sync()).  `dst` must
+        hold the DELAYED frame's size (next_output())."""
+        produced = self._produced; ots = self._ots
+        rc = self.lib.lvk_hip_stab_push_obs_host(self.handle, src["vf"], src["ptrs"], src["steps"], src["rows"], src["cols"], timestamp,
+                                                 dst["ptrs"], dst["steps"], dst["rows"], self._produced_ref, self._ots_ref, None)
+        if rc != 0:
+            self.ctx._check(rc)
+        return (dst["planes"], ots.value) if produced.value else (None, None)
+
     # ---- StabilizationFilter (Filters/StabilizationFilter.hpp:46-62)
     def restart(self):
         self.ctx._check(self.lib.lvk_hip_stab_restart(self.handle)); self._borrowed.clear()
