@@ -29,8 +29,14 @@ public:
     {
         const int f = lvk_hip_obs_frame_format(obs_format);
         if (f < 0) return nullptr;
-        if (f == LVK_FORMAT_GRAY) return nullptr;             // Y800: a one-channel VideoFrame, which this facade's VideoFrame (8UC3) does not model; the C-ABI converts it
+        if (f == LVK_FORMAT_GRAY) return nullptr;             // Y800: a one-channel frame, not a three-channel one -- SelectY800() below
         return std::unique_ptr<FrameIngest>(new FrameIngest(obs_format, static_cast<VideoFrame::Format>(f), ctx));
+    }
+    // Y800 (DirectIngest, FrameIngest.cpp:728-753): the one plane as a one-channel VideoFrame::GRAY frame (8UC1), which StabilizationFilter::apply,
+    // WarpMesh::apply and lvk::remap take.  A selector of its own: Select() keeps answering nullptr for Y800, as its callers expect of it.
+    static std::unique_ptr<FrameIngest> SelectY800(const std::shared_ptr<hip::Context>& ctx = nullptr)
+    {
+        return std::unique_ptr<FrameIngest>(new FrameIngest(LVK_VIDEO_FORMAT_Y800, VideoFrame::GRAY, ctx));
     }
 
     int obs_format() const { return m_OBSFormat; }                         // :128-131
@@ -65,7 +71,7 @@ public:
             m_ctx->check(lvk_hip_upload(m_ctx->get(), d, src->data[i], (size_t)pl[i].step * pl[i].rows), "FrameIngest::upload_obs_frame");
             d_planes[i] = d; steps[i] = pl[i].step;
         }
-        dst.create({cols, rows}, CV_8UC3, m_ctx);
+        dst.create({cols, rows}, VideoFrame::type_of(m_OCLFormat), m_ctx);
         m_ctx->check(lvk_hip_ingest_obs(m_ctx->get(), m_OBSFormat, d_planes, steps, rows, cols, dst.device_ptr(), (int)dst.step), "FrameIngest::upload_obs_frame");
         m_ctx->check(lvk_hip_sync(m_ctx->get()), "FrameIngest::upload_obs_frame");       // the host planes are the caller's again
         dst.timestamp = src->timestamp;                                                  // :99-101
@@ -134,6 +140,7 @@ private:
         case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: case LVK_VIDEO_FORMAT_UYVY: set(0, rows, 2 * cols); return 1;
         case LVK_VIDEO_FORMAT_AYUV: set(0, rows, 4 * cols); return 1;
         case LVK_VIDEO_FORMAT_BGR3: set(0, rows, 3 * cols); return 1;
+        case LVK_VIDEO_FORMAT_Y800: set(0, rows, cols); return 1;
         case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX:
             set(0, rows, 4 * cols); pl[0].written_bytes = 3 * cols; pl[0].linear = true; return 1;
         }

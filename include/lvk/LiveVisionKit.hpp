@@ -854,10 +854,15 @@ private:
         VideoFrame result;
         lvk_frame_info due{0, 0, 0}, emitted{0, 0, 0};
         const int will_emit = lvk_hip_stab_next_output(m_Stab, in.rows, in.cols, (int)in.format, &due);
-        if (will_emit == 1) result.create({due.cols, due.rows}, CV_8UC3, m_OutCtx);
+        // a GRAY frame (8UC1: what FrameIngest makes of Y800) goes through lvk_hip_stab_push_gray; a queue holds one format class (restart() to switch)
+        const bool gray = in.format == VideoFrame::GRAY;
+        LVK_HIP_ASSERT(in.channels() == (gray ? 1 : 3));
+        if (will_emit == 1) result.create({due.cols, due.rows}, due.format == LVK_FORMAT_GRAY ? CV_8UC1 : CV_8UC3, m_OutCtx);
         int produced = 0; uint64_t ts = 0; const void* released = nullptr;
         m_Held.push_back({in.buffer(), in.context()});     // keep the borrowed device buffer alive while it is queued
-        const int rc = lvk_hip_stab_push(m_Stab, in.device_ptr(), (int)in.step, in.rows, in.cols, in.timestamp, (int)in.format,
+        const int rc = gray ? lvk_hip_stab_push_gray(m_Stab, in.device_ptr(), (int)in.step, in.rows, in.cols, in.timestamp,
+                                                     result.device_ptr(), (int)result.step, result.rows, &produced, &ts, &released, &emitted)
+                            : lvk_hip_stab_push(m_Stab, in.device_ptr(), (int)in.step, in.rows, in.cols, in.timestamp, (int)in.format,
                                          result.device_ptr(), (int)result.step, result.rows, &produced, &ts, &released, &emitted);
         if (rc == LVK_HIP_ERR_ARG) m_Held.pop_back();      // (a refused push has queued nothing; after any other error the frame may be queued: keep it alive)
         m_Ctx->check(rc, "StabilizationFilter::filter");

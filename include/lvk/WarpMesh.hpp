@@ -154,10 +154,15 @@ inline void remap(const VideoFrame& src, VideoFrame& dst, const OffsetMap& offse
     const auto& ctx = src.context();
     if (offset_map.context() && offset_map.context() != ctx) ctx->wait_for(*offset_map.context());
     VideoFrame out;                                        // dst may be the object src refers to
-    out.create(src.size(), CV_8UC3, ctx);
+    LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3);
+    out.create(src.size(), src.type(), ctx);               // 8UC3, or 8UC1 (a GRAY frame: the one-channel kernels, background[0])
     const uint8_t bg[3] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2]};
     {
         hip::ContextLock lock(ctx->mutex());
+        if (src.channels() == 1)
+            ctx->check(lvk_hip_remap_map_gray(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
+                                              offset_map.device_ptr(), (int)offset_map.step, bg[0]), "remap(offset_map)");
+        else
         ctx->check(lvk_hip_remap_map(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
                                      offset_map.device_ptr(), (int)offset_map.step, bg, src.format == VideoFrame::YUV ? 1 : 0), "remap(offset_map)");
     }
@@ -175,10 +180,15 @@ inline void remap(const VideoFrame& src, VideoFrame& dst, const Homography& homo
     for (int i = 0; i < 9; i++) H[i] = (float)t.data()[i];
     const auto& ctx = src.context();
     VideoFrame out;
-    out.create(src.size(), CV_8UC3, ctx);
+    LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3);
+    out.create(src.size(), src.type(), ctx);               // 8UC3, or 8UC1 (a GRAY frame)
     const uint8_t bg[3] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2]};
     {
         hip::ContextLock lock(ctx->mutex());
+        if (src.channels() == 1)
+            ctx->check(lvk_hip_remap_homography_gray(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, out.rows, out.cols,
+                                                     0, 0, H, bg[0]), "remap(homography)");
+        else
         ctx->check(lvk_hip_remap_homography(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, out.rows, out.cols,
                                             0, 0, H, bg, src.format == VideoFrame::YUV ? 1 : 0), "remap(homography)");
     }
@@ -323,8 +333,13 @@ public:
         }
         else
         {
-            out.create(src.size(), CV_8UC3, ctx);
+            LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3);
+            out.create(src.size(), src.type(), ctx);           // 8UC3, or 8UC1 (a GRAY frame: lvk_hip_warpmesh_apply_gray, background[0])
             hip::ContextLock lock(ctx->mutex());
+            if (src.channels() == 1)
+                ctx->check(lvk_hip_warpmesh_apply_gray(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
+                                                       m.off.data(), m.rows, m.cols, bg[0]), "WarpMesh::apply");
+            else
             ctx->check(lvk_hip_warpmesh_apply(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
                                               m.off.data(), m.rows, m.cols, bg, src.format == VideoFrame::YUV ? 1 : 0), "WarpMesh::apply");
         }

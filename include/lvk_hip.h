@@ -175,8 +175,8 @@ int lvk_hip_egress_yuv420(lvk_hip_ctx* ctx, const void* d_src, int src_step, int
  *   I444 / YUVA                   merge / split (:521,531)
  *   YUY2 / YVYU / UYVY            P422Ingest::to_ocl / to_obs (:615-666): 2 bytes per pixel, chroma shared by a pixel pair
  *   AYUV                          P444Ingest (:679-703): the last three of A Y U V in; A = 255 out
- *   Y800 / BGR3                   DirectIngest (:728-753): the bytes as they are (Y800: a one-channel frame, which lvk_hip_stab_push refuses like the
- *                                 reference's lvk::remap does, Functions/Image.cpp:32)
+ *   Y800 / BGR3                   DirectIngest (:728-753): the bytes as they are (Y800: a one-channel frame, which lvk_hip_stab_push and the plane entries
+ *                                 refuse like the reference's lvk::remap does, Functions/Image.cpp:32; lvk_hip_stab_push_gray of PART 2 takes it)
  *   RGBA / BGRA / BGRX            DirectIngest as written: rows * cols * 3 BYTES from data[0] viewed as 3-byte pixels (:743-747) -- the colour planes are
  *                                 not separated; steps[0] must be 4 * cols.  Reproduced, not endorsed.
  * cols even for the 4:2:2 formats, rows and cols even for 4:2:0.  The frame is 8UC3 (Y800: 8UC1) of rows x cols; lvk_hip_obs_frame_format gives the
@@ -327,8 +327,9 @@ int  lvk_hip_stab_push_yuv420(lvk_hip_stab* stab, const void* d_y, int y_step, c
                               int rows, int cols, uint64_t timestamp,
                               void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int o_rows,
                               int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
-/* The same call for ANY video format FrameIngest::Select accepts except Y800 (LVK_VIDEO_FORMAT_*; d_planes / steps as for lvk_hip_ingest_obs, o_planes /
- * o_steps / o_rows the planes of the emitted frame and their row capacity): I420 / I40A / NV12 take lvk_hip_stab_push_yuv420's route; the other formats
+/* The same call for ANY three-channel video format FrameIngest::Select accepts; Y800, a one-channel frame, goes through lvk_hip_stab_push_gray of PART 2.
+ * video_format is an LVK_VIDEO_FORMAT_*; d_planes / steps are as for lvk_hip_ingest_obs; o_planes / o_steps / o_rows are the planes of the emitted frame
+ * and their row capacity.  I420 / I40A / NV12 take lvk_hip_stab_push_yuv420's route; the other formats
  * are converted into the filter's frame pool (FrameIngest::to_ocl), pushed, and the emitted frame -- the DELAYED one, at its own size -- converted back
  * (::to_obs).  Input planes consumed when the call returns; output planes complete after lvk_hip_sync(); planes that cannot hold the emitted frame are
  * refused before anything changes.  Shares the frame queue with lvk_hip_stab_push_yuv420.
@@ -357,7 +358,8 @@ int  lvk_hip_stab_push_yuv420_host(lvk_hip_stab* stab, const void* h_y, int y_st
                                    int rows, int cols, uint64_t timestamp,
                                    void* oh_y, int oy_step, void* oh_u, int ou_step, void* oh_v, int ov_step, int o_rows,
                                    int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
-/* The host entry for ANY video format FrameIngest::Select accepts except Y800 (ABI 12): the contract of lvk_hip_stab_push_obs with h_planes / oh_planes
+/* The host entry for ANY three-channel video format FrameIngest::Select accepts (ABI 12); Y800, a one-channel frame, goes through lvk_hip_stab_push_gray_host
+ * of PART 2.  It is the contract of lvk_hip_stab_push_obs with h_planes / oh_planes
  * in PINNED host memory -- what FrameIngest::upload_planes / download_planes do for every format alike (FrameIngest.cpp:415-474).  I420 / I40A / NV12
  * are handed to lvk_hip_stab_push_yuv420_host unchanged (as lvk_hip_stab_push_obs hands them to lvk_hip_stab_push_yuv420).  Plane geometry per format
  * as for lvk_hip_ingest_obs / lvk_hip_egress_obs: 4:2:2 planar chroma cols / 2 wide and rows high; packed 4:2:2 2 * cols bytes a row; AYUV 4 * cols;
@@ -500,6 +502,45 @@ int  lvk_hip_stab_prefetch(lvk_hip_stab* stab, const void* d_frame, int step, in
 int  lvk_hip_stab_prefetch_yuv420(lvk_hip_stab* stab, const void* d_y, int y_step, const void* d_u, int u_step, const void* d_v, int v_step,
                                   int nv12, int rows, int cols);
 long long lvk_hip_stab_lookahead_frames(lvk_hip_stab* stab);
+
+/* ---- one-channel (8UC1, LVK_FORMAT_GRAY) frames: what FrameIngest makes of Y800, a monochrome or IR camera ---------------------------------------
+ * The reference's lvk::remap asserts CV_8UC3 (Functions/Image.cpp:32); the algorithm does not need three channels.  DEFINITION:
+ * the reference's non-YUV EASU program reads the luma of its edge analysis as channel 0 of the pixel, so its twelve tap weights depend on channel 0
+ * alone, and each channel is accumulated, normalised, clamped and converted on its own.  The remap of a one-channel frame g is channel 0 of that
+ * program run on the three-channel frame (g, c, c) for any constant c, with background (bg, *, *); border, nearest-neighbour and background rules
+ * unchanged.  Bit-identical to channel 0 of the three-channel entry with yuv = 0 on (g, c, c).
+ * The five entries mirror their three-channel namesakes of PART 1 (same arguments, same refusals, step >= cols) with ONE background byte and no
+ * `yuv` argument; in addition source and destination byte ranges that overlap are refused (LVK_HIP_ERR_ARG, the destination untouched).  Any pitch
+ * and any byte alignment of either frame.  A 2 x 2 mesh goes through cv::getPerspectiveTransform and the homography kernel. */
+int lvk_hip_remap_homography_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
+                                  void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], uint8_t bg);
+int lvk_hip_remap_mesh_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step,
+                            const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg);
+int lvk_hip_remap_map_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                           const void* d_map, int map_step, uint8_t bg);
+int lvk_hip_warpmesh_apply_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                                const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg);
+int lvk_hip_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                                     const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const lvk_camera_params* lens);
+/* The stabilization filter on one-channel device frames: the contract of the packed-frame push of PART 1 (borrowed frame, *released, overlap mode, the
+ * DELAYED frame emitted at its own size into a d_out of out_rows rows of out_step >= cols bytes, a push whose output would not fit refused before
+ * anything changes) with step >= cols and format LVK_FORMAT_GRAY throughout.  The tracker reads the frame as its own luma; the remap is the
+ * one-channel one above with background[0].  The next-output query of PART 1 reports the delayed frame with format LVK_FORMAT_GRAY: one byte per pixel.
+ * ONE FORMAT CLASS PER STREAM: a queue that holds three-channel frames refuses a GRAY push, and a queue that holds GRAY frames refuses every
+ * three-channel push, with LVK_HIP_ERR_ARG before anything changes; lvk_hip_stab_restart recovers.  The three-channel entries keep refusing
+ * LVK_FORMAT_GRAY / Y800 themselves.  The test-mode overlays (draw_trackers, draw_motion_mesh) draw three bytes per pixel and are refused on a GRAY
+ * queue; stable_region, stabilize_output = 0 and crop_to_stable_region work as for three channels.  Look-ahead is out of scope for GRAY. */
+int  lvk_hip_stab_push_gray(lvk_hip_stab* stab, const void* d_frame, int step, int rows, int cols, uint64_t timestamp,
+                            void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released,
+                            lvk_frame_info* emitted);
+/* The same push for a frame in PINNED host memory, one plane each way: h_frame is uploaded on the filter's upload stream into a block the library owns
+ * until that frame has been emitted (the host plane is the caller's again when the call returns), and the one-channel remap stores the emitted frame
+ * straight into oh_out, a pinned plane of out_rows rows of out_step >= cols bytes (complete after lvk_hip_sync).  Size rule, format class, overlap mode
+ * as above.  Refused with LVK_HIP_ERR_ARG before anything is uploaded or queued: everything lvk_hip_stab_push_gray refuses, a pageable input or output
+ * plane (either end of its extent), frames borrowed by lvk_hip_stab_push_gray still queued (and the reverse: the two do not share a queue;
+ * lvk_hip_stab_restart recovers), and a push while frames announced through lvk_hip_stab_prefetch_yuv420_host are outstanding. */
+int  lvk_hip_stab_push_gray_host(lvk_hip_stab* stab, const void* h_frame, int step, int rows, int cols, uint64_t timestamp,
+                                 void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
 
 /* Which schedule the pushes of this filter took so far.  The library picks per push, from what it sees the caller doing (is the bulk stream still
  * busy with the previous remap? did this push begin within 15 us of the last one's return?), between the schedule of a FREE-RUNNING caller

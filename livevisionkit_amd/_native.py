@@ -35,6 +35,16 @@ _SIG = {
     "lvk_hip_remap_mesh": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int,
                                       _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.POINTER(_c.c_uint8), _c.c_int]),
     "lvk_hip_remap_map": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_uint8), _c.c_int]),
+    "lvk_hip_remap_homography_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int,
+                                                 _c.c_int, _c.c_int, _c.POINTER(_c.c_float), _c.c_uint8]),
+    "lvk_hip_remap_mesh_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.c_uint8]),
+    "lvk_hip_remap_map_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_uint8]),
+    "lvk_hip_warpmesh_apply_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.c_uint8]),
+    "lvk_hip_warpmesh_apply_lens_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.c_uint8, _P]),
+    "lvk_hip_stab_push_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_uint64, _P, _c.c_int, _c.c_int,
+                                          _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _c.POINTER(_P), _P]),
+    "lvk_hip_stab_push_gray_host": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_uint64, _P, _c.c_int, _c.c_int,
+                                               _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _P]),
     "lvk_hip_upscale": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_sharpen": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
     "lvk_hip_native_rcp": (_c.c_int, [_P, _P, _P, _c.c_size_t]),

@@ -126,6 +126,52 @@ class Context:
             mp, m.shape[0], m.shape[1], bgp, 1 if yuv else 0))
         return out
 
+    # ---- one-channel (GRAY) frames: channel 0 of the non-YUV EASU program on (g, c, c); src / out: torch uint8 [rows, cols] -------------
+    def _gray_out(self, src, out, shape=None):
+        import torch
+        if src.dim() != 2:
+            raise ValueError("a one-channel frame is a [rows, cols] uint8 tensor")
+        return out if out is not None else torch.empty(shape or tuple(src.shape), dtype=torch.uint8, device=src.device)
+
+    def remap_homography_gray(self, src, H, bg=0, out=None, dst_size=None, offset=(0, 0)):
+        """lvk_hip_remap_homography_gray: remap_homography for a one-channel frame, one background byte."""
+        rows, cols = src.shape
+        drows, dcols = dst_size if dst_size is not None else (rows, cols)
+        out = self._gray_out(src, out, (drows, dcols))
+        Ha, Hp = _f32(np.asarray(H, dtype=np.float32).reshape(9))
+        self._check(self.lib.lvk_hip_remap_homography_gray(self.handle, src.data_ptr(), src.stride(0), rows, cols, out.data_ptr(), out.stride(0), drows, dcols,
+                                                           offset[0], offset[1], Hp, int(bg)))
+        return out
+
+    def remap_mesh_gray(self, src, mesh, bg=0, out=None):
+        """lvk_hip_remap_mesh_gray: remap_mesh for a one-channel frame."""
+        out = self._gray_out(src, out)
+        m = np.ascontiguousarray(mesh, dtype=np.float32)
+        ma, mp = _f32(m)
+        self._check(self.lib.lvk_hip_remap_mesh_gray(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
+                                                     mp, m.shape[0], m.shape[1], int(bg)))
+        return out
+
+    def remap_map_gray(self, src, offsets, bg=0, out=None):
+        """lvk_hip_remap_map_gray: remap_map for a one-channel frame (offsets: torch float32 [rows, cols, 2] on the GPU, pixels)."""
+        out = self._gray_out(src, out)
+        self._check(self.lib.lvk_hip_remap_map_gray(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
+                                                    offsets.data_ptr(), offsets.stride(0) * 4, int(bg)))
+        return out
+
+    def warpmesh_apply_gray(self, src, mesh, bg=0, out=None, lens=None):
+        """lvk_hip_warpmesh_apply_gray (lens = camera params: lvk_hip_warpmesh_apply_lens_gray): WarpMesh::apply on a one-channel frame."""
+        out = self._gray_out(src, out)
+        m = np.ascontiguousarray(mesh, dtype=np.float32)
+        ma, mp = _f32(m)
+        args = (self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0), mp, m.shape[0], m.shape[1], int(bg))
+        if lens is None:
+            self._check(self.lib.lvk_hip_warpmesh_apply_gray(*args))
+        else:
+            arr = (ctypes.c_double * 9)(*[float(v) for v in lens])
+            self._check(self.lib.lvk_hip_warpmesh_apply_lens_gray(*args, arr))
+        return out
+
     # ---- a3/a4/a7 image ops --------------------------------------------------------------------------
     def luma_area_resize(self, frame, drows, dcols, channel=0):
         """frame: torch uint8 [rows, cols, 3] (packed) or [rows, cols] (planar) -> [drows, dcols] uint8."""

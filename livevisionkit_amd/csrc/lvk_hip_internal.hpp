@@ -381,6 +381,17 @@ int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, hipStream_t stream, const v
                                    void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv,
                                    const LensArgs* lens, bool co_scheduled = false);   // co_scheduled: occupancy-capped kernels for overlap mode
 
+// Dense remap of one-channel (8UC1) frames (remap_gray.hip): channel 0 of the non-YUV EASU program on (g, c, c); bg = the background byte
+int lvk_launch_remap_homography_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
+                                     void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y,
+                                     const float H[9], uint8_t bg, const LensArgs* lens = nullptr, bool co_scheduled = false);
+int lvk_launch_remap_mesh_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                               const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const LensArgs* lens = nullptr, bool co_scheduled = false);
+int lvk_launch_remap_map_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
+                              void* d_dst, int dst_step, const void* d_map, int map_step, uint8_t bg);
+int lvk_launch_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                                        const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const LensArgs* lens, bool co_scheduled = false);   // co_scheduled: the persistent grid of the overlap mode (same kernel body)
+
 // Debug overlays (draw.hip)
 int lvk_launch_draw_grid(lvk_hip_ctx* ctx, hipStream_t stream, void* d_dst, int dst_step, int rows, int cols, int grid_w, int grid_h,
                          const uint8_t colour[3], int thickness);

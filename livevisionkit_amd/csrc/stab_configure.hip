@@ -315,6 +315,8 @@ void lvk_hip_stab_destroy(lvk_hip_stab* st)
     st->pyr[0].release(); st->pyr[1].release();
     st->free_pool();
     st->free_hostio();
+    if (st->remap_stream) (void)hipStreamSynchronize(st->remap_stream);
+    st->free_gray_host();
     if (st->remap_stream)
     {
         (void)hipStreamSynchronize(st->remap_stream);
@@ -485,6 +487,7 @@ int lvk_hip_stab_draw_trackers(lvk_hip_stab* st)
     LVK_HIP_REQUIRE(st->ctx, !st->queue.empty());                                           // StreamBuffer::newest: !is_empty()
     st->finish_post();
     const QueuedFrame& f = st->queue.back();
+    if (f.format == LVK_FORMAT_GRAY) return st->fail(LVK_HIP_ERR_ARG, "draw_trackers: the overlay kernels draw three bytes per pixel; a GRAY queue is refused (nothing was drawn)");
     double r[3], g[3], b[3];
     overlay_colours(f.format, r, g, b);
     uint8_t col[3];
@@ -503,6 +506,7 @@ int lvk_hip_stab_draw_motion_mesh(lvk_hip_stab* st)
     lvk_device_guard device_guard(st->ctx);
     LVK_HIP_REQUIRE(st->ctx, !st->queue.empty());
     const QueuedFrame& f = st->queue.back();
+    if (f.format == LVK_FORMAT_GRAY) return st->fail(LVK_HIP_ERR_ARG, "draw_motion_mesh: the overlay kernels draw three bytes per pixel; a GRAY queue is refused (nothing was drawn)");
     double r[3], g[3], b[3];
     overlay_colours(f.format, r, g, b);
     const uint8_t col[3] = {(uint8_t)b[0], (uint8_t)b[1], (uint8_t)b[2]};

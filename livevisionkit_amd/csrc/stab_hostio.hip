@@ -46,6 +46,15 @@ int lvk_hip_stab::ensure_hostio(int rows, int cols, size_t in_bytes)
     return LVK_HIP_OK;
 }
 
+// the blocks lvk_hip_stab_push_gray_host still owns (the streams that read them have been synchronised by the caller)
+void lvk_hip_stab::free_gray_host()
+{
+    for (void* p : gray_host_live) (void)lvk_hip_free(ctx, p);
+    gray_host_live.clear();
+    if (gray_up_done) { (void)hipEventDestroy(gray_up_done); gray_up_done = nullptr; }
+    if (gray_fence) { (void)hipEventDestroy(gray_fence); gray_fence = nullptr; }
+}
+
 void lvk_hip_stab::free_hostio()
 {
     HostIO& h = hostio;
@@ -345,7 +354,8 @@ int lvk_hip_stab_push_yuv420_host(lvk_hip_stab* st, const void* h_y, int y_step,
     return LVK_HIP_OK;
 }
 
-// The host entry for EVERY OBS video format FrameIngest::Select accepts (except Y800): lvk_hip_stab_push_obs with the planes in pinned host memory --
+// The host entry for EVERY three-channel OBS video format FrameIngest::Select accepts; Y800, a one-channel frame, goes through lvk_hip_stab_push_gray_host
+// below.  It is lvk_hip_stab_push_obs with the planes in pinned host memory --
 // what FrameIngest::upload_planes / download_planes do for every format alike (Modules/OBS-Plugin/Interop/FrameIngest.cpp:415-474).  I420 / I40A / NV12
 // are lvk_hip_stab_push_yuv420_host's.  The other formats share its machinery:
 //   in:  the planes go through the one upload stream into a staging slot sized for the format; planar formats luma first with its own event (the tracker
@@ -416,6 +426,85 @@ int lvk_hip_stab_push_obs_host(lvk_hip_stab* st, int video_format, const void* c
     if ((rc = st->flush_download(false)) != LVK_HIP_OK) return rc;
     if (produced) *produced = prod;
     io.last_end = std::chrono::steady_clock::now();
+    return LVK_HIP_OK;
+}
+
+// The host entry for ONE-channel frames (Y800 / VideoFrame::GRAY): lvk_hip_stab_push_gray with the plane in pinned host memory, one plane each way.
+//   in:  one copy on the upload stream into a block of the context's pool that the entry owns until its frame has been emitted (the queue holds whole
+//        frames); the tracker's stream waits for the copy's event; the host plane is the caller's again when the call returns;
+//   out: the one-channel remap stores into the caller's pinned plane itself (no download route).
+// Refused before anything is uploaded or queued: what lvk_hip_stab_push_gray refuses (sizes, a short step, the other format class in the queue, an output
+// plane that does not hold the DELAYED frame), frames that lvk_hip_stab_push_gray borrowed still queued, pageable planes, outstanding 4:2:0 look-ahead.
+int lvk_hip_stab_push_gray_host(lvk_hip_stab* st, const void* h_frame, int step, int rows, int cols, uint64_t timestamp,
+                                void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted)
+{
+    if (!st) return LVK_HIP_ERR_ARG;
+    if (produced) *produced = 0;
+    lvk_device_guard device_guard(st->ctx);
+    lvk_hip_ctx* ctx = st->ctx;
+    LVK_HIP_REQUIRE(ctx, h_frame && rows > 0 && cols > 0 && step >= cols);
+    if (!st->buffers_ok) return ctx->fail(LVK_HIP_ERR_RUNTIME, "the last configure() failed while allocating the tracker's buffers: configure again");
+    int rc;
+    QueuedFrame due{}; bool will_emit = false;
+    if ((rc = lvk_stab_check_gray(st, true, rows, cols, timestamp, oh_out, out_step, out_rows, &due, &will_emit)) != LVK_HIP_OK) return rc;
+    if (!st->hostio.ahead.empty())
+        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_gray_host: frames announced through lvk_hip_stab_prefetch_yuv420_host have not been pushed yet -- push them "
+                                         "or lvk_hip_stab_prefetch_cancel() first; nothing was queued");
+    const HostPlane in{h_frame, step, cols, rows};
+    if ((rc = st->require_pinned_planes(&in, 1, "lvk_hip_stab_push_gray_host")) != LVK_HIP_OK) return rc;
+    if (oh_out && out_step >= (will_emit ? due.cols : cols) && out_rows >= (will_emit ? due.rows : rows))
+    {
+        const HostPlane out{oh_out, out_step, will_emit ? due.cols : cols, will_emit ? due.rows : rows};
+        if ((rc = st->require_pinned_planes(&out, 1, "lvk_hip_stab_push_gray_host (output)")) != LVK_HIP_OK) return rc;
+    }
+    // blocks whose frame left the queue outside a push (restart, a shrinking queue): nothing may still read them
+    {
+        bool synced = false;
+        for (size_t i = 0; i < st->gray_host_live.size();)
+        {
+            void* p = st->gray_host_live[i];
+            bool queued = p == st->pending_release;
+            for (const QueuedFrame& q : st->queue) queued = queued || q.d_ptr == p;
+            if (queued) { i++; continue; }
+            if (!synced) { LVK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); if (st->remap_stream) LVK_HIP_CHECK(ctx, hipStreamSynchronize(st->remap_stream)); synced = true; }
+            (void)lvk_hip_free(ctx, p);
+            st->gray_host_live.erase(st->gray_host_live.begin() + (long)i);
+        }
+        st->orphaned.clear();                                  // (they were this entry's blocks, freed above)
+    }
+    if ((rc = st->host_stream(st->hostio.up)) != LVK_HIP_OK) return rc;
+    if (!st->gray_up_done) LVK_HIP_CHECK(ctx, hipEventCreateWithFlags(&st->gray_up_done, hipEventDisableTiming));
+    if (!st->gray_fence) LVK_HIP_CHECK(ctx, hipEventCreateWithFlags(&st->gray_fence, hipEventDisableTiming));
+    void* d_frame = nullptr;
+    if ((rc = lvk_hip_malloc(ctx, (size_t)rows * cols, &d_frame)) != LVK_HIP_OK) return rc;
+    // the block may have been read last by a remap on the tracking stream that has not run yet (no overlap: a frame is released as soon as its remap is
+    // enqueued): the upload follows whatever that stream holds.  In overlap mode a frame is released only after its remap has finished.
+    hipStream_t up = st->hostio.up;
+    hipError_t e = hipEventRecord(st->gray_fence, ctx->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(up, st->gray_fence, 0);
+    if (e == hipSuccess) e = step == cols ? hipMemcpyAsync(d_frame, h_frame, (size_t)rows * cols, hipMemcpyHostToDevice, up)
+                                          : hipMemcpy2DAsync(d_frame, (size_t)cols, h_frame, (size_t)step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipEventRecord(st->gray_up_done, up);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, st->gray_up_done, 0);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(up); (void)lvk_hip_free(ctx, d_frame); return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(e)); }
+    st->gray_host_live.push_back(d_frame);
+    HostPushHooks clear_hooks{st};
+    struct EntryFlag { lvk_hip_stab* s; ~EntryFlag() { s->gray_host_entry_now = false; } } entry_flag{st};
+    st->gray_host_entry_now = true;
+    st->host_direct_now = will_emit;                               // the remap's stores cross the host link
+    int prod = 0; const void* released = nullptr;
+    rc = lvk_hip_stab_push_gray(st, d_frame, cols, rows, cols, timestamp, oh_out, out_step, out_rows, &prod, out_timestamp, &released, emitted);
+    const hipError_t se = hipEventSynchronize(st->gray_up_done);    // "consumed on return": the host plane is the caller's again
+    auto drop = [&](const void* p) {
+        auto it = std::find(st->gray_host_live.begin(), st->gray_host_live.end(), p);
+        if (it != st->gray_host_live.end()) { (void)lvk_hip_free(ctx, *it); st->gray_host_live.erase(it); }
+    };
+    if (rc == LVK_HIP_ERR_ARG) drop(d_frame);                       // (a refused push has queued nothing)
+    if (released) drop(released);
+    if (rc != LVK_HIP_OK) return rc;
+    if (se != hipSuccess) return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(se));
+    if (produced) *produced = prod;
+    st->hostio.last_end = std::chrono::steady_clock::now();
     return LVK_HIP_OK;
 }
 

@@ -366,24 +366,36 @@ int lvk_hip_stab::track(const QueuedFrame& f, const void* luma, int luma_step, i
     return LVK_HIP_OK;
 }
 
+static const char* lvk_frame_format_name(int f);
+
 // StabilizationFilter::filter (StabilizationFilter.cpp:69-135).  (luma, luma_step, luma_pix): where the tracker reads the
 // luma of this frame from -- the packed frame itself (pix 3) or, on the YUV420 path, the caller's planar Y (pix 1).
 
 int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows, int cols, uint64_t timestamp, int format,
                      const void* luma, int luma_step, int luma_pix,
                      void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released, OutPlanes420* o420,
-                     lvk_frame_info* emitted)
+                     lvk_frame_info* emitted, bool gray_entry)
 {
     lvk_hip_ctx* ctx = st->ctx;
     if (produced) *produced = 0;
     if (released) *released = nullptr;
-    LVK_HIP_REQUIRE(ctx, d_frame && rows > 0 && cols > 0 && step >= 3 * cols);           // !input.empty()
+    // bytes per pixel of this push's frames: the GRAY entries (lvk_hip_stab_push_gray*) queue one-channel frames, every other entry three-channel ones
+    const int bpp = gray_entry ? 1 : 3;
+    if (gray_entry) LVK_HIP_REQUIRE(ctx, d_frame && rows > 0 && cols > 0 && step >= cols && format == LVK_FORMAT_GRAY && luma_pix == 1);
+    else LVK_HIP_REQUIRE(ctx, d_frame && rows > 0 && cols > 0 && step >= 3 * cols);           // !input.empty()
     if (!st->buffers_ok) return ctx->fail(LVK_HIP_ERR_RUNTIME, "the last configure() failed while allocating the tracker's buffers: configure again");
     // 3-channel VideoFrame formats (VideoFrame.cpp:170-306): YUV tracks channel 0, BGR / RGB track cvtColor(..2GRAY); the remap
-    // runs the YUV or the RGB EASU program by the frame's format (Image.cpp:36-41).  GRAY / 4-channel frames are not on this path.
-    LVK_HIP_REQUIRE(ctx, format == LVK_FORMAT_YUV || format == LVK_FORMAT_BGR || format == LVK_FORMAT_RGB);
-    const int luma_channel = format == LVK_FORMAT_YUV ? 0 : (format == LVK_FORMAT_BGR ? -1 : -2);
-    LVK_HIP_REQUIRE(ctx, luma_pix == 3 || format == LVK_FORMAT_YUV);
+    // runs the YUV or the RGB EASU program by the frame's format (Image.cpp:36-41).  4-channel frames are not on this path; GRAY frames -- their own
+    // luma, remapped by the one-channel kernels (remap_gray.hip) -- only through the GRAY entries.
+    if (!gray_entry) LVK_HIP_REQUIRE(ctx, format == LVK_FORMAT_YUV || format == LVK_FORMAT_BGR || format == LVK_FORMAT_RGB);
+    const int luma_channel = (gray_entry || format == LVK_FORMAT_YUV) ? 0 : (format == LVK_FORMAT_BGR ? -1 : -2);
+    if (!gray_entry) LVK_HIP_REQUIRE(ctx, luma_pix == 3 || format == LVK_FORMAT_YUV);
+    // One format class per stream, like the plane entries (lvk_stab_check_due): the emitted frame leaves through THIS push's output buffer, whose pixel size is
+    // that of this push's class -- a queue that holds three-channel frames refuses a GRAY push and the reverse, before anything changes; restart() recovers.
+    for (const QueuedFrame& q : st->queue)
+        if ((q.format == LVK_FORMAT_GRAY) != gray_entry)
+            return ctx->fail(LVK_HIP_ERR_ARG, std::string("a frame of this stream was queued as ") + lvk_frame_format_name(q.format) + " and this push's frame is " +
+                                                  lvk_frame_format_name(format) + ": one-channel and three-channel frames do not share a queue -- restart() before switching; nothing was queued");
     const QueuedFrame in{d_frame, step, rows, cols, timestamp, format};
     // The frame this push will emit is the DELAYED one, at its own size (the queue holds whole frames, StabilizationFilter.cpp:118-131; dst is
     // allocated from the delayed source, WarpMesh.cpp:183-223 -> Image.cpp:53,116): what cannot be written is refused HERE, before the tracker
@@ -397,7 +409,7 @@ int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows
             const bool planes_fit = !o420 || o420->vf != 0 ||
                                     (o420->y && o420->y_step >= due.cols && o420->u_step >= (o420->nv12 ? due.cols : due.cols / 2) &&
                                      (o420->nv12 || o420->v_step >= due.cols / 2) && o420->rows_cap >= due.rows);
-            const bool fits = planes_fit && (to_planes || (d_out != nullptr && out_step >= 3 * due.cols && out_rows >= due.rows));
+            const bool fits = planes_fit && (to_planes || (d_out != nullptr && out_step >= bpp * due.cols && out_rows >= due.rows));
             if (!fits)
                 return ctx->fail(LVK_HIP_ERR_ARG, "the output buffer does not hold the frame this push emits: " + std::to_string(due.cols) + " x " + std::to_string(due.rows) +
                                                       " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
@@ -469,11 +481,13 @@ int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows
                                                o420->nv12, mesh->off.data(), mesh->rows, mesh->cols, bg, lens_args, persistent);
             o420->used = true;
         }
+        else if (mesh && gray_entry) rc = lvk_launch_warpmesh_apply_lens_gray(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg[0],
+                                                                              lens_args, persistent);
         else if (mesh) rc = lvk_launch_warpmesh_apply_lens(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg,
                                                       f.format == LVK_FORMAT_YUV ? 1 : 0, lens_args, persistent);
         else
         {
-            hipError_t e = hipMemcpy2DAsync(d_out, out_step, f.d_ptr, f.step, (size_t)f.cols * 3, f.rows, hipMemcpyDeviceToDevice, ctx->stream);
+            hipError_t e = hipMemcpy2DAsync(d_out, out_step, f.d_ptr, f.step, (size_t)f.cols * bpp, f.rows, hipMemcpyDeviceToDevice, ctx->stream);
             if (e != hipSuccess) rc = ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(e));
         }
         st->prof_end(pe, rs);
@@ -674,7 +688,7 @@ int lvk_stab_check_in_planes(lvk_hip_stab* st, int vf, const void* const in_plan
     lvk_hip_ctx* ctx = st->ctx;
     *frame_format = lvk_hip_obs_frame_format(vf);
     if (*frame_format < 0 || *frame_format == LVK_FORMAT_GRAY || !in_planes || !in_steps || !in_planes[0])
-        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs: video format " + std::to_string(vf) + " has no three-channel frame the filter could take (FrameIngest::Select, lvk::remap: CV_8UC3)");
+        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_obs: video format " + std::to_string(vf) + " has no three-channel frame the filter could take (FrameIngest::Select, lvk::remap: CV_8UC3; a Y800 frame goes through lvk_hip_stab_push_gray)");
     // what the conversion will read (planes, pitches, the parity of the size) is checked HERE, before the pool, the tracker or the queue changes: in overlap
     // mode the conversion itself is launched only after track() and the queue have moved, and a refusal there left an unconverted slot queued
     return lvk_ingest_obs_check(ctx, vf, in_planes, in_steps, rows, cols);
@@ -713,6 +727,29 @@ int lvk_stab_check_due(lvk_hip_stab* st, int vf, int frame_format, int rows, int
     return LVK_HIP_OK;
 }
 
+int lvk_stab_check_gray(lvk_hip_stab* st, bool host, int rows, int cols, uint64_t timestamp, const void* d_out, int out_step, int out_rows,
+                        lvkstab::QueuedFrame* due_out, bool* will_emit_out)
+{
+    if (!st->queue.empty() && st->queue_kind == 2)
+        return st->fail(LVK_HIP_ERR_ARG, "frames of lvk_hip_stab_push_yuv420 / lvk_hip_stab_push_obs are still queued: restart() before switching to a GRAY push; nothing was queued");
+    for (const QueuedFrame& q : st->queue)
+    {
+        if (q.format != LVK_FORMAT_GRAY)
+            return st->fail(LVK_HIP_ERR_ARG, std::string("a frame of this stream was queued as ") + lvk_frame_format_name(q.format) + " and this push's frame is GRAY"
+                                                 ": one-channel and three-channel frames do not share a queue -- restart() before switching; nothing was queued");
+        if (st->gray_host_owns(q.d_ptr) != host)
+            return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_gray borrows its frames and lvk_hip_stab_push_gray_host owns them: restart() before switching between the two; nothing was queued");
+    }
+    QueuedFrame due{};
+    const bool will_emit = rows > 0 && cols > 0 && st->next_output(QueuedFrame{nullptr, cols, rows, cols, timestamp, LVK_FORMAT_GRAY}, &due);
+    if (will_emit && !(d_out != nullptr && out_step >= due.cols && out_rows >= due.rows))
+        return st->fail(LVK_HIP_ERR_ARG, "the output buffer does not hold the frame this push emits: " + std::to_string(due.cols) + " x " + std::to_string(due.rows) +
+                                             " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
+    if (due_out) *due_out = due;
+    if (will_emit_out) *will_emit_out = will_emit;
+    return LVK_HIP_OK;
+}
+
 extern "C" {
 
 int lvk_hip_stab_next_output(const lvk_hip_stab* st, int rows, int cols, int format, lvk_frame_info* out)
@@ -740,6 +777,36 @@ int lvk_hip_stab_push(lvk_hip_stab* st, const void* d_frame, int step, int rows,
     int rc = st->mark_caller_work();
     if (rc != LVK_HIP_OK) return rc;
     rc = lvk_stab_push_impl(st, d_frame, step, rows, cols, timestamp, format, d_frame, step, 3, d_out, out_step, out_rows, produced, out_timestamp, released, nullptr, emitted);
+    if (released && !*released && !st->orphaned.empty()) { *released = st->orphaned.front(); st->orphaned.pop_front(); }
+    st->trace.mark(HostTrace::EXIT);
+    st->last_push_end = std::chrono::steady_clock::now();
+    return rc;
+}
+
+// lvk_hip_stab_push for ONE-channel frames (VideoFrame::GRAY; what FrameIngest makes of Y800): the frame is its own tracking luma (pixel stride 1, channel 0)
+// and the delayed frame leaves through the one-channel remap (remap_gray.hip) with background[0].  Borrowed frames, the size rule, overlap and *released as
+// for lvk_hip_stab_push; a queue holds frames of one format class only (lvk_stab_push_impl refuses the other before anything changes).
+int lvk_hip_stab_push_gray(lvk_hip_stab* st, const void* d_frame, int step, int rows, int cols, uint64_t timestamp,
+                           void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released, lvk_frame_info* emitted)
+{
+    if (!st) return LVK_HIP_ERR_ARG;
+    lvk_device_guard device_guard(st->ctx);
+    st->trace.begin();
+    st->prof_tick++;
+    st->push_seq++;
+    struct AnnouncementEnds { lvk_hip_stab* s; ~AnnouncementEnds() { s->ahead_announced = lvk_hip_stab::LumaAhead(); } } announcement_ends{st};
+    if (produced) *produced = 0;
+    if (released) *released = nullptr;
+    // (the queue's owner and format class are checked before queue_kind / pool_frames are written: a refused push leaves everything as it was)
+    int rc = lvk_stab_check_gray(st, st->gray_host_entry_now, rows, cols, timestamp, d_out, out_step, out_rows, nullptr, nullptr);
+    if (rc != LVK_HIP_OK) return rc;
+    if (st->queue.empty()) st->queue_kind = 0;
+    st->queue_kind = 1;
+    st->pool_frames = false;
+    rc = st->mark_caller_work();
+    if (rc != LVK_HIP_OK) return rc;
+    rc = lvk_stab_push_impl(st, d_frame, step, rows, cols, timestamp, LVK_FORMAT_GRAY, d_frame, step, 1, d_out, out_step, out_rows, produced, out_timestamp, released, nullptr,
+                            emitted, true);
     if (released && !*released && !st->orphaned.empty()) { *released = st->orphaned.front(); st->orphaned.pop_front(); }
     st->trace.mark(HostTrace::EXIT);
     st->last_push_end = std::chrono::steady_clock::now();
@@ -918,7 +985,8 @@ int lvk_hip_stab_push_yuv420(lvk_hip_stab* st, const void* d_y, int y_step, cons
                                 out_planes, out_steps, o_rows, produced, out_timestamp, emitted);
 }
 
-// The plugin's asynchronous path for ANY format FrameIngest::Select accepts (except Y800), one call per frame: to_ocl -> StabilizationFilter::filter
+// The plugin's asynchronous path for ANY three-channel format FrameIngest::Select accepts, one call per frame; Y800, a one-channel frame, goes through
+// lvk_hip_stab_push_gray.  The steps: to_ocl -> StabilizationFilter::filter
 // -> to_obs (Modules/OBS-Plugin/Interop/VisionFilter.cpp:151-212, FrameIngest.cpp:36-75).
 int lvk_hip_stab_push_obs(lvk_hip_stab* st, int video_format, const void* const d_planes[3], const int steps[3], int rows, int cols, uint64_t timestamp,
                           void* const o_planes[3], const int o_steps[3], int o_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted)

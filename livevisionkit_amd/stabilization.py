@@ -163,19 +163,27 @@ class StabilizationFilter:
         """apply(std::move(input), output, profile): returns (output tensor, its timestamp) or (None, None) while the delay builds.
         `frame` is borrowed (not copied) until it has been emitted; do not modify it in the meantime.  The output has the size of the
         DELAYED frame (a stream whose frame size changes emits the queued frames at their own size): `out`, when given, must hold it
-        (next_output()), and the returned tensor is its top-left rows x cols view; self.last_format = that frame's format."""
+        (next_output()), and the returned tensor is its top-left rows x cols view; self.last_format = that frame's format.
+        A [rows, cols] tensor is a one-channel (GRAY) frame: it goes through lvk_hip_stab_push_gray and the output is [rows, cols] too."""
         import torch
         if profile:
             self.ctx.sync()
         t0 = time.perf_counter()
+        gray = frame.dim() == 2                                  # a [rows, cols] tensor is a one-channel (GRAY) frame: lvk_hip_stab_push_gray
+        if gray:
+            fmt = FORMAT_GRAY
         if out is None:
             due = self.next_output(frame.shape[0], frame.shape[1], fmt)
-            out = torch.empty((due[0], due[1], 3), dtype=torch.uint8, device=frame.device) if due else None
+            out = torch.empty((due[0], due[1]) if gray else (due[0], due[1], 3), dtype=torch.uint8, device=frame.device) if due else None
         produced = _c.c_int(0); ots = _c.c_uint64(0); released = _c.c_void_p(); info = FrameInfo()
-        rc = self.lib.lvk_hip_stab_push(self.handle, frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1],
-                                        int(timestamp), fmt, out.data_ptr() if out is not None else None, out.stride(0) if out is not None else 0,
-                                        out.shape[0] if out is not None else 0,
-                                        _c.byref(produced), _c.byref(ots), _c.byref(released), _c.byref(info))
+        optr, ostep, orows = (out.data_ptr(), out.stride(0), out.shape[0]) if out is not None else (None, 0, 0)
+        if gray:
+            rc = self.lib.lvk_hip_stab_push_gray(self.handle, frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1], int(timestamp),
+                                                 optr, ostep, orows, _c.byref(produced), _c.byref(ots), _c.byref(released), _c.byref(info))
+        else:
+            rc = self.lib.lvk_hip_stab_push(self.handle, frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1],
+                                            int(timestamp), fmt, optr, ostep, orows,
+                                            _c.byref(produced), _c.byref(ots), _c.byref(released), _c.byref(info))
         self.ctx._check(rc)                                      # (a refused push has queued nothing: the frame is still the caller's)
         self._borrowed[frame.data_ptr()] = frame
         if released.value:
@@ -335,6 +343,36 @@ class StabilizationFilter:
         if rc != 0:
             self.ctx._check(rc)
         return (dst["planes"], ots.value) if produced.value else (None, None)
+
+    # ---- host-resident one-channel frames (lvk_hip_stab_push_gray_host)
+    def host_plane_gray(self, rows, cols, pitch_extra=0):
+        """One pinned [rows, cols] uint8 plane (a numpy view of a lvk_hip_host_malloc block), every row `pitch_extra` bytes longer than its pixels."""
+        import numpy as np
+        step = cols + pitch_extra
+        p = _c.c_void_p()
+        self.ctx._check(self.lib.lvk_hip_host_malloc(self.ctx.handle, rows * step, _c.byref(p)))
+        self._host_blocks = getattr(self, "_host_blocks", []); self._host_blocks.append(p)
+        return np.ctypeslib.as_array((_c.c_uint8 * (rows * step)).from_address(p.value)).reshape(rows, step)[:, :cols]
+
+    def apply_gray_host(self, plane, timestamp=0, out=None):
+        """lvk_hip_stab_push_gray_host: a one-channel frame in a pinned host plane in (numpy uint8 [rows, cols], host_plane_gray), the emitted frame -- the
+        DELAYED one, at its own size (next_output()) -- written into the pinned plane `out` (complete after Context.sync()).  Returns (the top-left view of
+        `out` that holds the frame, its timestamp) or (None, None) while the delay builds."""
+        t0 = time.perf_counter()
+        rows, cols = plane.shape
+        if out is None:
+            due = self.next_output(rows, cols, FORMAT_GRAY)
+            out = self.host_plane_gray(due[0], due[1]) if due else None
+        produced = _c.c_int(0); ots = _c.c_uint64(0); info = FrameInfo()
+        optr, ostep, orows = (out.ctypes.data, out.strides[0], out.shape[0]) if out is not None else (None, 0, 0)
+        rc = self.lib.lvk_hip_stab_push_gray_host(self.handle, plane.ctypes.data, plane.strides[0], rows, cols, int(timestamp), optr, ostep, orows,
+                                                  _c.byref(produced), _c.byref(ots), _c.byref(info))
+        self.ctx._check(rc)
+        self._timer._add(time.perf_counter() - t0)
+        if not produced.value:
+            return None, None
+        self.last_format = info.format
+        return out[:info.rows, :info.cols], ots.value
 
     # ---- host-resident frames of any OBS video format (lvk_hip_stab_push_obs_host)
     @staticmethod
