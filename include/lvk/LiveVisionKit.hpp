@@ -46,6 +46,10 @@ inline std::function<void(std::string, std::string, std::string)> assert_handler
 }
 #define LVK_HIP_ASSERT(cond) do { if (!(cond)) lvk::context::assert_handler("LiveVisionKit.hpp", __func__, #cond); } while (0)
 
+// The arithmetic of the three-channel EASU remap (MI355X addition; lvk_hip.h LVK_REMAP_EXACT / LVK_REMAP_1LSB).  Exact: bit-identical to the reference's
+// kernels compiled for this chip, the default everywhere.  OneLSB: the tap weights algebraically regrouped -- fewer instructions, every byte within 1.
+enum class RemapPrecision { Exact = LVK_REMAP_EXACT, OneLSB = LVK_REMAP_1LSB };
+
 // ---------------------------------------------------------------------------------------------- hip context
 namespace hip {
 // One HIP context (stream + staging) per object that needs one; replaces OpenCV's implicit OpenCL queue.
@@ -75,6 +79,18 @@ public:
         std::scoped_lock lock(m_mutex, producer.m_mutex);         // both, deadlock-free whatever the order two threads name them in
         check(lvk_hip_ctx_wait(m_ctx, producer.m_ctx), "Context::wait_for");
     }
+    // The precision of the stateless three-channel remaps enqueued through this context -- lvk::remap, WarpMesh::apply -- from now on
+    // (lvk_hip_set_remap_precision).  A StabilizationFilter has its own setting.
+    void set_remap_precision(const RemapPrecision precision)
+    {
+        ContextLockGuard lock(m_mutex);
+        check(lvk_hip_set_remap_precision(m_ctx, static_cast<int>(precision)), "Context::set_remap_precision");
+    }
+    RemapPrecision remap_precision() const
+    {
+        ContextLockGuard lock(m_mutex);
+        return static_cast<RemapPrecision>(lvk_hip_get_remap_precision(m_ctx));
+    }
     Context(const Context&) = delete;
     Context& operator=(const Context&) = delete;
     lvk_hip_ctx* get() const { return m_ctx; }
@@ -83,6 +99,7 @@ public:
         if (rc < 0) lvk::context::assert_handler("LiveVisionKit.hpp", what, lvk_hip_last_error(m_ctx));
     }
 private:
+    using ContextLockGuard = std::lock_guard<std::recursive_mutex>;
     lvk_hip_ctx* m_ctx = nullptr;
     mutable std::recursive_mutex m_mutex;
 };
@@ -715,6 +732,18 @@ public:
         m_Ctx->check(lvk_hip_stab_set_bulk_context(m_Stab, enable ? m_BulkCtx->get() : nullptr), "set_overlap");
         m_Overlap = enable;
         refresh_output_context();
+    }
+    // The precision of this filter's output remap from the next emitted frame on (lvk_hip_stab_set_remap_precision): nothing restarts, the queue and
+    // the trajectory are kept.  A filter is created Exact whatever its context's setting; GRAY frames stay exact in both.
+    void set_remap_precision(const RemapPrecision precision)
+    {
+        hip::ContextLock lock(m_Ctx->mutex());
+        m_Ctx->check(lvk_hip_stab_set_remap_precision(m_Stab, static_cast<int>(precision)), "set_remap_precision");
+    }
+    RemapPrecision remap_precision() const
+    {
+        hip::ContextLock lock(m_Ctx->mutex());
+        return static_cast<RemapPrecision>(lvk_hip_stab_get_remap_precision(m_Stab));
     }
     // Fused lens pre-warp (BASELINE config 5): frames are pushed RAW, the lens correction of the plugin's LCFilter
     // (Modules/OBS-Plugin/Sources/Enhancement/LCFilter.cpp:133-192) is composed into the stabilizing remap.  Restarts the filter.

@@ -118,6 +118,21 @@ int lvk_hip_remap_mesh(lvk_hip_ctx* ctx,
 int lvk_hip_remap_map(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
                       const void* d_map, int map_step, const uint8_t bg[3], int yuv);
 
+/* Remap precision (opt-in; added to PART 1 without a version increment: no existing signature or contract changes, and EXACT is the default everywhere).
+ * LVK_REMAP_1LSB runs the same EASU -- same 12 taps, same direction analysis, same normalised colours, same clamp and truncation -- with the twelve tap
+ * weights algebraically regrouped: fewer instructions in the kernel that bounds a 4K stream, every output byte within 1 of EXACT's (the tolerance
+ * SURVEY.md section 8c grants the remap; specification tests/np_easu_1lsb.py).  Border-band and background pixels never
+ * reach the weights and are identical.
+ * lvk_hip_set_remap_precision governs the stateless three-channel remap entries of THIS context: lvk_hip_remap_homography / _mesh / _map,
+ * lvk_hip_warpmesh_apply, lvk_hip_warpmesh_apply_lens and lvk_hip_warpmesh_apply_yuv420.  A stabilizer has its own setting
+ * (lvk_hip_stab_set_remap_precision) and is created EXACT whatever its context says.  Exact in every mode: the one-channel remaps of PART 2,
+ * lvk_hip_upscale, lvk_hip_fsr_easu, lvk_hip_sharpen.  An unknown value is refused with LVK_HIP_ERR_ARG and changes nothing; get returns the
+ * current value (LVK_HIP_ERR_ARG for a NULL context). */
+#define LVK_REMAP_EXACT 0   /* bit-identical to the reference's kernels compiled for this chip (default) */
+#define LVK_REMAP_1LSB  1   /* every output byte within 1 of EXACT; fewer instructions */
+int lvk_hip_set_remap_precision(lvk_hip_ctx* ctx, int precision);
+int lvk_hip_get_remap_precision(lvk_hip_ctx* ctx);
+
 /* lvk::upscale(src, dst, size, yuv) (Functions/Image.cpp:155-202, kernel easu_scale FSR.cl:324-358): EASU upsampling of an
  * 8UC3 frame to dst_cols x dst_rows >= the source size (equal size = copy).  d_dst must not alias d_src. */
 int lvk_hip_upscale(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
@@ -406,6 +421,12 @@ int  lvk_hip_stab_set_bulk_context(lvk_hip_stab* stab, lvk_hip_ctx* bulk);
  * stream): enqueue stream-ordered consumers of d_out / the output planes (a D2H copy, an encoder) there instead of calling
  * lvk_hip_sync().  Changes when lvk_hip_stab_set_overlap or stabilize_output change. */
 void* lvk_hip_stab_output_stream(lvk_hip_stab* stab);
+/* The remap precision of THIS stabilizer's output (LVK_REMAP_EXACT / LVK_REMAP_1LSB, see lvk_hip_set_remap_precision): takes effect on the next emitted
+ * frame -- the queue, the trajectory and the tracker's state are kept, nothing restarts, no stream is waited for.  Valid with overlap on or off and for
+ * every push entry; the GRAY pushes of PART 2 accept the setting and stay exact.  A stabilizer is created EXACT.  An unknown value is refused with
+ * LVK_HIP_ERR_ARG and changes nothing. */
+int  lvk_hip_stab_set_remap_precision(lvk_hip_stab* stab, int precision);
+int  lvk_hip_stab_get_remap_precision(const lvk_hip_stab* stab);
 
 
 /* ---- the deblocking filter ----------------------------------------------------------------------------------------------------------

@@ -5,7 +5,7 @@ the C++ facade in include/lvk/.  This Python package is the thin host-side mirro
 bench driver: it calls the C-ABI through ctypes and uses torch only for device memory and streams.
 """
 from . import _native
-from .context import Context, LvkHipError
+from .context import Context, LvkHipError, REMAP_EXACT, REMAP_1LSB
 from .stabilization import StabilizationFilter, StabilizationFilterSettings
 from .deblocking import DeblockingFilter, DeblockingFilterSettings
 from .cas import CASFilter
@@ -14,6 +14,6 @@ from .fsr import FSRFilter, fsr_geometry, easu_const
 from .draw import draw_points, draw_rect, draw_text, text_size
 from . import shard
 
-__all__ = ["Context", "LvkHipError", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "CASFilter",
+__all__ = ["Context", "LvkHipError", "REMAP_EXACT", "REMAP_1LSB", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "CASFilter",
            "ConversionFilter", "reformat", "FSRFilter", "fsr_geometry", "easu_const", "draw_points", "draw_rect",
            "draw_text", "text_size", "_native"]

@@ -45,6 +45,10 @@ _SIG = {
                                           _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _c.POINTER(_P), _P]),
     "lvk_hip_stab_push_gray_host": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_uint64, _P, _c.c_int, _c.c_int,
                                                _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _P]),
+    "lvk_hip_set_remap_precision": (_c.c_int, [_P, _c.c_int]),
+    "lvk_hip_get_remap_precision": (_c.c_int, [_P]),
+    "lvk_hip_stab_set_remap_precision": (_c.c_int, [_P, _c.c_int]),
+    "lvk_hip_stab_get_remap_precision": (_c.c_int, [_P]),
     "lvk_hip_upscale": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_sharpen": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
     "lvk_hip_native_rcp": (_c.c_int, [_P, _P, _P, _c.c_size_t]),

@@ -46,6 +46,15 @@ class TrackChainResult(ctypes.Structure):
                 ("mirror_status", ctypes.POINTER(ctypes.c_uint8)),
                 ("next_pts", ctypes.POINTER(ctypes.c_float)), ("flow_status", ctypes.POINTER(ctypes.c_uint8)), ("flow_und", ctypes.POINTER(ctypes.c_float))]
 
+REMAP_EXACT, REMAP_1LSB = 0, 1          # LVK_REMAP_EXACT / LVK_REMAP_1LSB of include/lvk_hip.h
+
+
+def _remap_precision(precision):
+    """The C-ABI value of a precision given as REMAP_EXACT / REMAP_1LSB or as "exact" / "1lsb"; anything else goes to the library, which refuses it."""
+    if isinstance(precision, str):
+        return {"exact": REMAP_EXACT, "1lsb": REMAP_1LSB}.get(precision.lower(), -1)
+    return int(precision)
+
 
 class Context:
     """One HIP stream + staging on one GPU (reference analogue: the implicit cv::ocl queue)."""
@@ -82,6 +91,16 @@ class Context:
 
     def sync(self):
         self._check(self.lib.lvk_hip_sync(self.handle))
+
+    def set_remap_precision(self, precision):
+        """REMAP_EXACT (default: bit-identical to the reference's kernels) or REMAP_1LSB (regrouped tap weights: fewer instructions, every byte within 1)
+        for the three-channel remaps of this context: remap_homography / _mesh / _map, warpmesh_apply and its lens / 4:2:0 forms.  Stabilizers have
+        their own setting; upscale, sharpen and the one-channel remaps are exact in both."""
+        self._check(self.lib.lvk_hip_set_remap_precision(self.handle, _remap_precision(precision)))
+
+    @property
+    def remap_precision(self):
+        return self.lib.lvk_hip_get_remap_precision(self.handle)
 
     # ---- a15/a16 -------------------------------------------------------------------------------
     def remap_homography(self, src, H, bg=(255, 0, 255), yuv=True, out=None, dst_size=None, offset=(0, 0)):

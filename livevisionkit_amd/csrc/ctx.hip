@@ -21,6 +21,18 @@ const char* lvk_hip_version(void) { return "lvk-hip 0.12 (gfx950, ABI 12)"; }
 
 int lvk_hip_abi_version(void) { return LVK_HIP_ABI_VERSION; }
 
+// The kernels of this context's stateless three-channel remap entries (remap.hip reads the field at every launch); stabilizers have their own setting
+int lvk_hip_set_remap_precision(lvk_hip_ctx* ctx, int precision)
+{
+    if (!ctx) return LVK_HIP_ERR_ARG;
+    if (precision != LVK_REMAP_EXACT && precision != LVK_REMAP_1LSB)
+        return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_set_remap_precision: unknown precision " + std::to_string(precision));
+    ctx->remap_precision = precision;
+    return LVK_HIP_OK;
+}
+
+int lvk_hip_get_remap_precision(lvk_hip_ctx* ctx) { return ctx ? ctx->remap_precision : LVK_HIP_ERR_ARG; }
+
 static bool device_is_gfx950(int d)
 {
     hipDeviceProp_t prop;

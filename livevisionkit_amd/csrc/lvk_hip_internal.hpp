@@ -26,6 +26,7 @@ struct PyrArgs { PyrLevel lv[LVK_MAX_PYR_LEVELS]; int nlevels; };
 
 struct lvk_hip_ctx
 {
+    int remap_precision = LVK_REMAP_EXACT;  // lvk_hip_set_remap_precision: the kernels of the stateless three-channel remap entries (a stabilizer has its own)
     int co_blocks_per_cu = 0;               // persistent remap grid of the overlap mode: blocks per CU for the next launch (0: the default)
     int device = 0;
     int cu_count = 0;                   // compute units of the device (persistent-grid sizing of the remap)
@@ -119,8 +120,7 @@ struct lvk_device_guard
 
 // Instrumented kernels (in-kernel clocks, printf) never go into the product library: the defines below are only accepted together with
 // -DLVK_PROBE_BUILD, which scripts/variant_build.sh passes for the variants under livevisionkit_amd/variants/ (round-4 ADVICE).
-// (the same for kernels that are NOT bit-exact: LVK_EASU_TOLERANT, the tolerance-mode A / B partner of the remap -- remap_core.hpp)
-#if (defined(LVK_TIMELINE) || defined(LVK_RANSAC_TIMING) || defined(LVK_MESH_TIMING) || defined(LVK_EASU_TOLERANT)) && !defined(LVK_PROBE_BUILD)
+#if (defined(LVK_TIMELINE) || defined(LVK_RANSAC_TIMING) || defined(LVK_MESH_TIMING)) && !defined(LVK_PROBE_BUILD)
 #error "instrumented build: pass -DLVK_PROBE_BUILD (scripts/variant_build.sh); never the library the tests and the bench load by default"
 #endif
 
@@ -313,15 +313,17 @@ struct LvkTrackChain
 int lvk_launch_track_chain(lvk_hip_ctx* ctx, const LvkTrackChain& c);
 
 struct LensArgs;
-// Dense remap on an explicit stream (remap.hip)
+// Dense remap on an explicit stream (remap.hip).  precision: LVK_REMAP_EXACT or LVK_REMAP_1LSB -- it selects the kernel of the ONE launch (the exact
+// kernel or its `_r1` twin); any other value is refused.  The caller decides where it comes from: the context's setting for the stateless entries,
+// the stabilizer's own for its emits.
 int lvk_launch_remap_homography(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
                                 void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y,
-                                const float H[9], const uint8_t bg[3], int yuv, const LensArgs* lens = nullptr, bool co_scheduled = false);
+                                const float H[9], const uint8_t bg[3], int yuv, const LensArgs* lens, bool co_scheduled, int precision);
 int lvk_launch_remap_mesh(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
                           void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv,
-                          const LensArgs* lens = nullptr, bool co_scheduled = false);
+                          const LensArgs* lens, bool co_scheduled, int precision);
 int lvk_launch_warpmesh_apply(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                              void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv);
+                              void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, int precision);
 
 // YUV420 <-> packed 444 (ingest.hip)
 int lvk_launch_ingest_yuv420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_y, int y_step, const void* d_u, int u_step,
@@ -336,7 +338,7 @@ int lvk_launch_egress_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format
 
 
 int lvk_launch_remap_map(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                         void* d_dst, int dst_step, const void* d_map, int map_step, const uint8_t bg[3], int yuv);
+                         void* d_dst, int dst_step, const void* d_map, int map_step, const uint8_t bg[3], int yuv, int precision);
 
 // Fused lens pre-warp (lens.hip): the camera profile reduced to what the closed-form map needs for one frame size.
 // d = nfx, nfy, ncx, ncy (new camera matrix), fx, fy, cx, cy, k1, k2, p1, p2, k3, kxc, vxc, kyc, vyc (crop_in term, pixels);
@@ -379,7 +381,7 @@ int lvk_launch_lens_undistort(lvk_hip_ctx* ctx, hipStream_t stream, const LensMo
 // lens != nullptr composes the closed-form lens map into the coordinate (fused mode)
 int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
                                    void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv,
-                                   const LensArgs* lens, bool co_scheduled = false);   // co_scheduled: occupancy-capped kernels for overlap mode
+                                   const LensArgs* lens, bool co_scheduled, int precision);   // co_scheduled: occupancy-capped kernels for overlap mode
 
 // Dense remap of one-channel (8UC1) frames (remap_gray.hip): channel 0 of the non-YUV EASU program on (g, c, c); bg = the background byte
 int lvk_launch_remap_homography_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
@@ -419,8 +421,8 @@ int lvk_launch_mesh_solve(lvk_mesh_solver_dev* s, hipStream_t stream, void* d_sc
 int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
                                   void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int nv12,
                                   const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const LensArgs* lens,
-                                  bool co_scheduled);
+                                  bool co_scheduled, int precision);
 bool lvk_remap_obs_fusable(int video_format);
 int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format, const void* d_src, int src_step, int rows, int cols,
                                   void* const planes[3], const int steps[3], const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3],
-                                  const LensArgs* lens, bool co);          // co_scheduled: the persistent grid of the overlap mode
+                                  const LensArgs* lens, bool co, int precision);          // co_scheduled: the persistent grid of the overlap mode

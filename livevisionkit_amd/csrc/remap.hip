@@ -9,113 +9,61 @@
 namespace {
 
 
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR
-void k_remap_homography(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                        uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols,
-                        int off_x, int off_y, HomographyArgs H, uint32_t bg)
+// (each LVK_REMAP_KERNEL* below defines the exact kernel NAME and its 1-LSB twin NAME_r1 from one body -- remap_core.hpp)
+LVK_REMAP_KERNEL_CO(bool YUV, k_remap_homography,
+                    (const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
+                     uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols,
+                     int off_x, int off_y, HomographyArgs H, uint32_t bg),
 {
     const HomographyCoord coord{H, off_x, off_y};
-    remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, dst_rows, dst_cols, coord, bg);
-}
+    remap_strip<YUV, W>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, dst_rows, dst_cols, coord, bg);
+})
 
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_homography_co(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                        uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols,
-                        int off_x, int off_y, HomographyArgs H, uint32_t bg)
-{
-    const HomographyCoord coord{H, off_x, off_y};
-    remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, dst_rows, dst_cols, coord, bg);
-}
-
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR
-void k_remap_mesh(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                  uint8_t* __restrict__ dst, int dst_step,
-                  const float* __restrict__ mesh, int mesh_cols, int mesh_floats,
-                  const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg)
+LVK_REMAP_KERNEL_CO(bool YUV, k_remap_mesh,
+                    (const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
+                     uint8_t* __restrict__ dst, int dst_step,
+                     const float* __restrict__ mesh, int mesh_cols, int mesh_floats,
+                     const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg),
 {
     if (mesh_to_lds(mesh, mesh_floats))
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, bg);
+        remap_strip<YUV, W>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, bg);
     else
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, bg);
-}
+        remap_strip<YUV, W>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, bg);
+})
 
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_mesh_co(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                  uint8_t* __restrict__ dst, int dst_step,
-                  const float* __restrict__ mesh, int mesh_cols, int mesh_floats,
-                  const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg)
-{
-    if (mesh_to_lds(mesh, mesh_floats))
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, bg);
-    else
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, bg);
-}
-
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR
-void k_remap_homography_lens(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                             uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols,
-                             int off_x, int off_y, HomographyArgs H, LensArgs L, uint32_t bg)
+LVK_REMAP_KERNEL_CO(bool YUV, k_remap_homography_lens,
+                    (const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
+                     uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols,
+                     int off_x, int off_y, HomographyArgs H, LensArgs L, uint32_t bg),
 {
     const LensCoord<HomographyCoord> coord{HomographyCoord{H, off_x, off_y}, L, src_rows, src_cols};
-    remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, dst_rows, dst_cols, coord, bg);
-}
+    remap_strip<YUV, W>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, dst_rows, dst_cols, coord, bg);
+})
 
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_homography_lens_co(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                             uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols,
-                             int off_x, int off_y, HomographyArgs H, LensArgs L, uint32_t bg)
-{
-    const LensCoord<HomographyCoord> coord{HomographyCoord{H, off_x, off_y}, L, src_rows, src_cols};
-    remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, dst_rows, dst_cols, coord, bg);
-}
-
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR
-void k_remap_mesh_lens(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                       uint8_t* __restrict__ dst, int dst_step,
-                       const float* __restrict__ mesh, int mesh_cols, int mesh_floats,
-                       const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, LensArgs L, uint32_t bg)
+LVK_REMAP_KERNEL_CO(bool YUV, k_remap_mesh_lens,
+                    (const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
+                     uint8_t* __restrict__ dst, int dst_step,
+                     const float* __restrict__ mesh, int mesh_cols, int mesh_floats,
+                     const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, LensArgs L, uint32_t bg),
 {
     if (mesh_to_lds(mesh, mesh_floats))
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols,
-                         LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, L, src_rows, src_cols}, bg);
+        remap_strip<YUV, W>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols,
+                            LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, L, src_rows, src_cols}, bg);
     else
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols,
-                         LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, L, src_rows, src_cols}, bg);
-}
+        remap_strip<YUV, W>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols,
+                            LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, L, src_rows, src_cols}, bg);
+})
 
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_mesh_lens_co(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                       uint8_t* __restrict__ dst, int dst_step,
-                       const float* __restrict__ mesh, int mesh_cols, int mesh_floats,
-                       const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, LensArgs L, uint32_t bg)
-{
-    if (mesh_to_lds(mesh, mesh_floats))
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols,
-                         LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, L, src_rows, src_cols}, bg);
-    else
-        remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols,
-                         LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)src_cols, (float)src_rows}, L, src_rows, src_cols}, bg);
-}
-
-template <bool YUV>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR
-void k_remap_map(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                 uint8_t* __restrict__ dst, int dst_step, const uint8_t* __restrict__ map, int map_step, uint32_t bg)
+LVK_REMAP_KERNEL(bool YUV, , k_remap_map,
+                 (const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
+                  uint8_t* __restrict__ dst, int dst_step, const uint8_t* __restrict__ map, int map_step, uint32_t bg),
 {
     const MapCoord coord{map, map_step};
-    remap_strip<YUV>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, coord, bg);
-}
+    remap_strip<YUV, W>(src, src_step, src_rows, src_cols, PackedSink{dst, dst_step}, src_rows, src_cols, coord, bg);
+})
 
 // lvk::upscale (Image.cpp:155-202): the same strip body; the source coordinate never leaves the image, so the border band is the
-// nearest copy of FSR.cl:342-351 and the background is unreachable.
+// nearest copy of FSR.cl:342-351 and the background is unreachable.  Exact in every remap precision: it has no 1-LSB twin.
 template <bool YUV>
 __global__ __launch_bounds__(256) LVK_REMAP_ATTR
 void k_easu_scale(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
@@ -129,45 +77,41 @@ void k_easu_scale(const uint8_t* __restrict__ src, int src_step, int src_rows, i
 //      the other kernels the overlap mode runs next to the tracker
 struct Planes420 { uint8_t* y; int y_step; uint8_t* u; int u_step; uint8_t* v; int v_step; };
 
-template <bool NV12>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_homography_420(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o, HomographyArgs H, uint32_t bg)
+LVK_REMAP_KERNEL(bool NV12, LVK_CO_SCHEDULED, k_remap_homography_420,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o, HomographyArgs H, uint32_t bg),
 {
     LVK_TL(0);
     const HomographyCoord coord{H, 0, 0};
-    remap_strip<true>(src, src_step, rows, cols, Sink420<NV12>{o.y, o.y_step, o.u, o.u_step, o.v, o.v_step}, rows, cols, coord, bg);
-}
+    remap_strip<true, W>(src, src_step, rows, cols, Sink420<NV12>{o.y, o.y_step, o.u, o.u_step, o.v, o.v_step}, rows, cols, coord, bg);
+})
 
-template <bool NV12>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_homography_lens_420(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o, HomographyArgs H, LensArgs L, uint32_t bg)
+LVK_REMAP_KERNEL(bool NV12, LVK_CO_SCHEDULED, k_remap_homography_lens_420,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o, HomographyArgs H, LensArgs L, uint32_t bg),
 {
     const LensCoord<HomographyCoord> coord{HomographyCoord{H, 0, 0}, L, rows, cols};
-    remap_strip<true>(src, src_step, rows, cols, Sink420<NV12>{o.y, o.y_step, o.u, o.u_step, o.v, o.v_step}, rows, cols, coord, bg);
-}
+    remap_strip<true, W>(src, src_step, rows, cols, Sink420<NV12>{o.y, o.y_step, o.u, o.u_step, o.v, o.v_step}, rows, cols, coord, bg);
+})
 
-template <bool NV12>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_mesh_420(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o,
-                      const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg)
+LVK_REMAP_KERNEL(bool NV12, LVK_CO_SCHEDULED, k_remap_mesh_420,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o,
+                  const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg),
 {
     const Sink420<NV12> sink{o.y, o.y_step, o.u, o.u_step, o.v, o.v_step};
-    if (mesh_to_lds(mesh, mesh_floats)) remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
-    else remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
-}
+    if (mesh_to_lds(mesh, mesh_floats)) remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
+    else remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
+})
 
-template <bool NV12>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_mesh_lens_420(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o,
-                           const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab,
-                           LensArgs L, uint32_t bg)
+LVK_REMAP_KERNEL(bool NV12, LVK_CO_SCHEDULED, k_remap_mesh_lens_420,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o,
+                  const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab,
+                  LensArgs L, uint32_t bg),
 {
     const Sink420<NV12> sink{o.y, o.y_step, o.u, o.u_step, o.v, o.v_step};
     if (mesh_to_lds(mesh, mesh_floats))
-        remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
+        remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
     else
-        remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
-}
+        remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
+})
 
 
 } // namespace
@@ -175,9 +119,10 @@ void k_remap_mesh_lens_420(const uint8_t* __restrict__ src, int src_step, int ro
 int lvk_launch_remap_homography(lvk_hip_ctx* ctx, hipStream_t stream,
                                 const void* d_src, int src_step, int src_rows, int src_cols,
                                 void* d_dst, int dst_step, int dst_rows, int dst_cols,
-                                int off_x, int off_y, const float H[9], const uint8_t bg[3], int yuv, const LensArgs* lens, bool co)
+                                int off_x, int off_y, const float H[9], const uint8_t bg[3], int yuv, const LensArgs* lens, bool co, int precision)
 {
     // Image.cpp:93-98
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(precision));
     LVK_HIP_REQUIRE(ctx, d_src != nullptr && d_dst != nullptr && H != nullptr && bg != nullptr);
     LVK_HIP_REQUIRE(ctx, src_cols > 0 && src_rows > 0 && dst_cols > 0 && dst_rows > 0);
     LVK_HIP_REQUIRE(ctx, src_step >= 3 * src_cols && dst_step >= 3 * dst_cols);
@@ -185,12 +130,18 @@ int lvk_launch_remap_homography(lvk_hip_ctx* ctx, hipStream_t stream,
     HomographyArgs args;
     std::memcpy(args.h, H, sizeof(args.h));
     const dim3 block(256), grid = remap_grid(dst_rows, dst_cols), cogrid = lvk_co_grid(ctx, dst_rows, dst_cols);
+    // one launch: the kernel is chosen by (precision, program, grid kind)
+#define LVK_LAUNCH_REMAP_CO(K, KCO, ...)                                                                                  \
+    do {                                                                                                                  \
+        if (yuv) { if (co) hipLaunchKernelGGL(KCO<true>, cogrid, block, 0, stream, __VA_ARGS__);                          \
+                   else hipLaunchKernelGGL(K<true>, grid, block, 0, stream, __VA_ARGS__); }                               \
+        else { if (co) hipLaunchKernelGGL(KCO<false>, cogrid, block, 0, stream, __VA_ARGS__);                             \
+               else hipLaunchKernelGGL(K<false>, grid, block, 0, stream, __VA_ARGS__); }                                  \
+    } while (0)
 #define LVK_LAUNCH_REMAP(K, ...)                                                                                          \
     do {                                                                                                                  \
-        if (yuv) { if (co) hipLaunchKernelGGL(K##_co<true>, cogrid, block, 0, stream, __VA_ARGS__);                       \
-                   else hipLaunchKernelGGL(K<true>, grid, block, 0, stream, __VA_ARGS__); }                               \
-        else { if (co) hipLaunchKernelGGL(K##_co<false>, cogrid, block, 0, stream, __VA_ARGS__);                          \
-               else hipLaunchKernelGGL(K<false>, grid, block, 0, stream, __VA_ARGS__); }                                  \
+        if (precision == LVK_REMAP_1LSB) LVK_LAUNCH_REMAP_CO(K##_r1, K##_co_r1, __VA_ARGS__);                             \
+        else LVK_LAUNCH_REMAP_CO(K, K##_co, __VA_ARGS__);                                                                 \
     } while (0)
     if (lens)
         LVK_LAUNCH_REMAP(k_remap_homography_lens, (const uint8_t*)d_src, src_step, src_rows, src_cols, (uint8_t*)d_dst, dst_step, dst_rows, dst_cols,
@@ -205,9 +156,10 @@ int lvk_launch_remap_homography(lvk_hip_ctx* ctx, hipStream_t stream,
 int lvk_launch_remap_mesh(lvk_hip_ctx* ctx, hipStream_t stream,
                           const void* d_src, int src_step, int src_rows, int src_cols,
                           void* d_dst, int dst_step,
-                          const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const LensArgs* lens, bool co)
+                          const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const LensArgs* lens, bool co, int precision)
 {
     // Image.cpp:30-34
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(precision));
     LVK_HIP_REQUIRE(ctx, d_src != nullptr && d_dst != nullptr && mesh != nullptr && bg != nullptr);
     LVK_HIP_REQUIRE(ctx, src_cols > 0 && src_rows > 0);
     LVK_HIP_REQUIRE(ctx, mesh_rows >= 2 && mesh_cols >= 2);           // WarpMesh::MinimumSize
@@ -233,6 +185,7 @@ int lvk_launch_remap_mesh(lvk_hip_ctx* ctx, hipStream_t stream,
         LVK_LAUNCH_REMAP(k_remap_mesh, (const uint8_t*)d_src, src_step, src_rows, src_cols, (uint8_t*)d_dst, dst_step, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2,
                          xtab, ytab, pack_bg(bg));
 #undef LVK_LAUNCH_REMAP
+#undef LVK_LAUNCH_REMAP_CO
     const hipError_t le = hipGetLastError();
     rc = lvk_stage_consumed(ctx, stage_slot, stream);               // the slot is free again once this kernel has read the mesh (also after a failed launch)
     if (le != hipSuccess) return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(le));
@@ -242,15 +195,21 @@ int lvk_launch_remap_mesh(lvk_hip_ctx* ctx, hipStream_t stream,
 // lvk::remap(src, dst, offset_map, background) with the map resident in HBM (Functions/Image.cpp:28-81): dst and map have
 // the size of src (the path never uses map ROIs).  d_map: rows x cols float2 offsets in pixels, pitch map_step bytes.
 int lvk_launch_remap_map(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                         void* d_dst, int dst_step, const void* d_map, int map_step, const uint8_t bg[3], int yuv)
+                         void* d_dst, int dst_step, const void* d_map, int map_step, const uint8_t bg[3], int yuv, int precision)
 {
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(precision));
     LVK_HIP_REQUIRE(ctx, d_src != nullptr && d_dst != nullptr && d_map != nullptr && bg != nullptr);     // Image.cpp:30-34
     LVK_HIP_REQUIRE(ctx, cols > 0 && rows > 0 && src_step >= 3 * cols && dst_step >= 3 * cols && map_step >= 8 * cols);
     LVK_HIP_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_map) | (uintptr_t)map_step) & 7u) == 0);
     LVK_HIP_REQUIRE(ctx, fits_u32(src_step, rows) && fits_u32(dst_step, rows) && fits_u32(map_step, rows));
     const dim3 block(256), grid = remap_grid(rows, cols);
-    if (yuv) hipLaunchKernelGGL(k_remap_map<true>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step, (const uint8_t*)d_map, map_step, pack_bg(bg));
-    else hipLaunchKernelGGL(k_remap_map<false>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step, (const uint8_t*)d_map, map_step, pack_bg(bg));
+#define LVK_LAUNCH_MAP(K)                                                                                                 \
+    do {                                                                                                                  \
+        if (yuv) hipLaunchKernelGGL(K<true>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step, (const uint8_t*)d_map, map_step, pack_bg(bg)); \
+        else hipLaunchKernelGGL(K<false>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step, (const uint8_t*)d_map, map_step, pack_bg(bg)); \
+    } while (0)
+    if (precision == LVK_REMAP_1LSB) LVK_LAUNCH_MAP(k_remap_map_r1); else LVK_LAUNCH_MAP(k_remap_map);
+#undef LVK_LAUNCH_MAP
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
 }
@@ -281,15 +240,15 @@ int lvk_launch_upscale(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, 
 int lvk_launch_warpmesh_apply(lvk_hip_ctx* ctx, hipStream_t stream,
                               const void* d_src, int src_step, int rows, int cols,
                               void* d_dst, int dst_step,
-                              const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv)
+                              const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, int precision)
 {
-    return lvk_launch_warpmesh_apply_lens(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, nullptr, false);
+    return lvk_launch_warpmesh_apply_lens(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, nullptr, false, precision);
 }
 
 int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, hipStream_t stream,
                                    const void* d_src, int src_step, int rows, int cols,
                                    void* d_dst, int dst_step,
-                                   const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const LensArgs* lens, bool co)
+                                   const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const LensArgs* lens, bool co, int precision)
 {
     LVK_HIP_REQUIRE(ctx, mesh != nullptr && mesh_rows >= 2 && mesh_cols >= 2);
     if (mesh_rows == 2 && mesh_cols == 2)
@@ -311,16 +270,17 @@ int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, hipStream_t stream,
             for (int q = 0; q < 9; q++) M[q] = (q % 4 == 0) ? 1.0 : 0.0;
         float H[9];
         for (int q = 0; q < 9; q++) H[q] = (float)M[q];              // Image.cpp:137-139
-        return lvk_launch_remap_homography(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, rows, cols, 0, 0, H, bg, yuv, lens, co);
+        return lvk_launch_remap_homography(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, rows, cols, 0, 0, H, bg, yuv, lens, co, precision);
     }
-    return lvk_launch_remap_mesh(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, lens, co);
+    return lvk_launch_remap_mesh(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, lens, co, precision);
 }
 
 // WarpMesh::apply + I4XXIngest / NV12Ingest::to_obs in one launch: d_src packed YUV 8UC3, output planar 4:2:0 (I420: y, u, v; NV12: y, uv).
 int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
                                   void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int nv12,
-                                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const LensArgs* lens, bool co)
+                                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const LensArgs* lens, bool co, int precision)
 {
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(precision));
     LVK_HIP_REQUIRE(ctx, d_src && o_y && o_u && (nv12 || o_v) && mesh && bg && mesh_rows >= 2 && mesh_cols >= 2);
     LVK_HIP_REQUIRE(ctx, rows > 0 && cols > 0 && (rows & 1) == 0 && (cols & 1) == 0 && src_step >= 3 * cols);
     LVK_HIP_REQUIRE(ctx, oy_step >= cols && ou_step >= (nv12 ? cols : cols / 2) && (nv12 || ov_step >= cols / 2));
@@ -329,6 +289,14 @@ int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, hipStream_t stream, const vo
     const dim3 block(256), grid = co ? lvk_co_grid(ctx, rows, cols) : remap_grid(rows, cols);
     const size_t lds_pad = co ? (size_t)LVK_CO_LDS_PAD : 0;          // A / B switch (scripts/variant_build.sh): unused LDS that caps the persistent grid's blocks per CU
     int stage_slot = -1;
+    // one launch: the kernel is chosen by (precision, plane layout)
+#define LVK_LAUNCH_420_(K, ...)                                                                                            \
+    do {                                                                                                                  \
+        if (nv12) hipLaunchKernelGGL(K<true>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, __VA_ARGS__, pack_bg(bg));   \
+        else hipLaunchKernelGGL(K<false>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, __VA_ARGS__, pack_bg(bg));       \
+    } while (0)
+#define LVK_LAUNCH_420(K, ...)                                                                                             \
+    do { if (precision == LVK_REMAP_1LSB) LVK_LAUNCH_420_(K##_r1, __VA_ARGS__); else LVK_LAUNCH_420_(K, __VA_ARGS__); } while (0)
     if (mesh_rows == 2 && mesh_cols == 2)
     {
         const float w = (float)cols, h = (float)rows;                 // WarpMesh.cpp:194-217, as in lvk_launch_warpmesh_apply_lens
@@ -344,16 +312,8 @@ int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, hipStream_t stream, const vo
             for (int q = 0; q < 9; q++) M[q] = (q % 4 == 0) ? 1.0 : 0.0;
         HomographyArgs args;
         for (int q = 0; q < 9; q++) args.h[q] = (float)M[q];
-        if (lens)
-        {
-            if (nv12) hipLaunchKernelGGL(k_remap_homography_lens_420<true>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, args, *lens, pack_bg(bg));
-            else hipLaunchKernelGGL(k_remap_homography_lens_420<false>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, args, *lens, pack_bg(bg));
-        }
-        else
-        {
-            if (nv12) hipLaunchKernelGGL(k_remap_homography_420<true>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, args, pack_bg(bg));
-            else hipLaunchKernelGGL(k_remap_homography_420<false>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, args, pack_bg(bg));
-        }
+        if (lens) LVK_LAUNCH_420(k_remap_homography_lens_420, args, *lens);
+        else LVK_LAUNCH_420(k_remap_homography_420, args);
     }
     else
     {
@@ -365,17 +325,11 @@ int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, hipStream_t stream, const vo
         if ((rc = lvk_get_lintab(ctx, mesh_rows, rows, true, &ytab)) != LVK_HIP_OK) return rc;
         void* d_mesh = nullptr;
         if ((rc = lvk_stage_params(ctx, stream, mesh, mesh_bytes, &d_mesh, &stage_slot)) != LVK_HIP_OK) return rc;
-        if (lens)
-        {
-            if (nv12) hipLaunchKernelGGL(k_remap_mesh_lens_420<true>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, *lens, pack_bg(bg));
-            else hipLaunchKernelGGL(k_remap_mesh_lens_420<false>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, *lens, pack_bg(bg));
-        }
-        else
-        {
-            if (nv12) hipLaunchKernelGGL(k_remap_mesh_420<true>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, pack_bg(bg));
-            else hipLaunchKernelGGL(k_remap_mesh_420<false>, grid, block, lds_pad, stream, (const uint8_t*)d_src, src_step, rows, cols, o, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, pack_bg(bg));
-        }
+        if (lens) LVK_LAUNCH_420(k_remap_mesh_lens_420, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, *lens);
+        else LVK_LAUNCH_420(k_remap_mesh_420, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab);
     }
+#undef LVK_LAUNCH_420
+#undef LVK_LAUNCH_420_
     const hipError_t le = hipGetLastError();
     const int src = stage_slot >= 0 ? lvk_stage_consumed(ctx, stage_slot, stream) : LVK_HIP_OK;
     if (le != hipSuccess) return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(le));
@@ -390,7 +344,7 @@ int lvk_hip_remap_homography(lvk_hip_ctx* ctx,
                              int off_x, int off_y, const float H[9], const uint8_t bg[3], int yuv)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_remap_homography(ctx, ctx->stream, d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols, off_x, off_y, H, bg, yuv);
+    return lvk_launch_remap_homography(ctx, ctx->stream, d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols, off_x, off_y, H, bg, yuv, nullptr, false, ctx->remap_precision);
 }
 
 int lvk_hip_remap_mesh(lvk_hip_ctx* ctx,
@@ -399,14 +353,14 @@ int lvk_hip_remap_mesh(lvk_hip_ctx* ctx,
                        const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_remap_mesh(ctx, ctx->stream, d_src, src_step, src_rows, src_cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv);
+    return lvk_launch_remap_mesh(ctx, ctx->stream, d_src, src_step, src_rows, src_cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, nullptr, false, ctx->remap_precision);
 }
 
 int lvk_hip_remap_map(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
                       const void* d_map, int map_step, const uint8_t bg[3], int yuv)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_remap_map(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, d_map, map_step, bg, yuv);
+    return lvk_launch_remap_map(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, d_map, map_step, bg, yuv, ctx->remap_precision);
 }
 
 int lvk_hip_warpmesh_apply_lens(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
@@ -418,7 +372,7 @@ int lvk_hip_warpmesh_apply_lens(lvk_hip_ctx* ctx, const void* d_src, int src_ste
     const int rc = lvk_lens_model_build(*lens, rows, cols, m);
     if (rc != LVK_HIP_OK) return ctx->fail(rc, "invalid camera profile");
     std::memcpy(a.f, m.f, sizeof(a.f));
-    return lvk_launch_warpmesh_apply_lens(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, &a, false);
+    return lvk_launch_warpmesh_apply_lens(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, &a, false, ctx->remap_precision);
 }
 
 int lvk_hip_warpmesh_apply_yuv420(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
@@ -427,7 +381,7 @@ int lvk_hip_warpmesh_apply_yuv420(lvk_hip_ctx* ctx, const void* d_src, int src_s
 {
     LVK_HIP_ENTRY(ctx);
     return lvk_launch_warpmesh_apply_420(ctx, ctx->stream, d_src, src_step, rows, cols, o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12,
-                                         mesh, mesh_rows, mesh_cols, bg, nullptr, false);
+                                         mesh, mesh_rows, mesh_cols, bg, nullptr, false, ctx->remap_precision);
 }
 
 int lvk_hip_upscale(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
@@ -443,7 +397,7 @@ int lvk_hip_warpmesh_apply(lvk_hip_ctx* ctx,
                            const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_warpmesh_apply(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv);
+    return lvk_launch_warpmesh_apply(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, ctx->remap_precision);
 }
 
 } // extern "C"

@@ -12,6 +12,8 @@
 // sequence the reference's OpenCL source compiles to for this device (the GPU tests check bit-identical
 // output): no implicit contraction (the file is compiled with -ffp-contract=off), fused multiply-adds exactly where clang's
 // FP_CONTRACT ON forms them (written as fma()), and native_recip / `1.0f / x` = the device reciprocal v_rcp_f32.
+// That contract is the default, LVK_REMAP_EXACT.  The opt-in LVK_REMAP_1LSB restates ONE stage, the tap weights (EasuRegrouped below; every byte within 1 of
+// the exact kernels'), in kernels of their own (`_r1`): the exact kernels do not change with it.
 //
 // Work decomposition: see remap_strip() -- 256 x 4 output strips, 4 pixels per thread, taps gathered with unaligned
 // dwordx2/x4 loads, XCD-aware strip order.
@@ -63,17 +65,9 @@ __device__ __forceinline__ F3 unpack3(uint32_t lo_bytes)   // bytes 0,1,2 of the
 {
     const float norm_factor = 0.00392156862f;               // FSR.cl:205
     F3 r;
-#if defined(LVK_EASU_TOLERANT) && LVK_EASU_TOLERANT >= 2
-    // (tolerance-mode A / B partner, level 2, never the product build: the colours stay in 0 .. 255, only the luma is normalised -- easu_core below)
-    (void)norm_factor;
-    r.x = (float)(lo_bytes & 0xffu);
-    r.y = (float)((lo_bytes >> 8) & 0xffu);
-    r.z = (float)((lo_bytes >> 16) & 0xffu);
-#else
     r.x = (float)(lo_bytes & 0xffu) * norm_factor;
     r.y = (float)((lo_bytes >> 8) & 0xffu) * norm_factor;
     r.z = (float)((lo_bytes >> 16) & 0xffu) * norm_factor;
-#endif
     return r;
 }
 
@@ -81,13 +75,7 @@ template <bool YUV>
 __device__ __forceinline__ float luma(const F3& p)
 {
     // FSR.cl:229-241 (the YUV program is the one that uses the 3-channel pseudo luma)
-#if defined(LVK_EASU_TOLERANT) && LVK_EASU_TOLERANT >= 2
-    // the direction analysis keeps the reference's scale: its bit-trick reciprocals (rcp_lo / rsq_lo) have a mantissa-dependent error of several
-    // percent, so an analysis on 255 x the luma would shape other kernels (> 1 LSB on edges); 0.5 x + y + 0.5 z is exact on bytes, one rounding follows
-    return (YUV ? fma_(p.z, 0.5f, fma_(p.x, 0.5f, p.y)) : p.x) * 0.00392156862f;
-#else
     return YUV ? fma_(p.z, 0.5f, fma_(p.x, 0.5f, p.y)) : p.x;
-#endif
 }
 
 __device__ __forceinline__ void accumulate(float& dirx, float& diry, float& len, float w,
@@ -149,8 +137,77 @@ __device__ __forceinline__ float4 make_tap(uint32_t lo_bytes)
     return make_float4(p.x, p.y, p.z, luma<YUV>(p));
 }
 
-// FSR.cl:181-318 on the 12 taps  b c / e f g h / i j k l / n o  (order of the array below).  Returns 0x00ZZYYXX.
-enum { TB, TC, TE, TF, TG, TH_, TI, TJ, TK, TL, TN, TO };
+enum { TB, TC, TE, TF, TG, TH_, TI, TJ, TK, TL, TN, TO };      // the 12 taps  b c / e f g h / i j k l / n o  in the order of easu_core's array
+
+// The weight stage of EASU -- the 12 window weights and the weighted sums (aC, aW) -- exists in two forms, chosen at compile time; everything around it
+// (direction analysis, colour normalisation, min / max clamp, x 255 truncation: easu_core) is the reference's sequence in both.
+//
+// EasuExact (LVK_REMAP_EXACT, the default everywhere): FSR.cl:98-126,299-313 operation for operation, in the reference's tap order.
+struct EasuExact
+{
+    static __device__ __forceinline__ void weights(const float4 t[12], float ppx, float ppy, float dirx, float diry, float len2x, float len2y,
+                                                   float lob, float clp, F3& aC, float& aW)
+    {
+#define LVK_TAP(ox, oy, T) tap(aC, aW, (ox) - ppx, (oy) - ppy, dirx, diry, len2x, len2y, lob, clp, F3{t[T].x, t[T].y, t[T].z})
+        LVK_TAP( 0.0f, -1.0f, TB);
+        LVK_TAP( 1.0f, -1.0f, TC);
+        LVK_TAP(-1.0f,  1.0f, TI);
+        LVK_TAP( 0.0f,  1.0f, TJ);
+        LVK_TAP( 0.0f,  0.0f, TF);
+        LVK_TAP(-1.0f,  0.0f, TE);
+        LVK_TAP( 1.0f,  1.0f, TK);
+        LVK_TAP( 2.0f,  1.0f, TL);
+        LVK_TAP( 2.0f,  0.0f, TH_);
+        LVK_TAP( 1.0f,  0.0f, TG);
+        LVK_TAP( 0.0f,  2.0f, TN);
+        LVK_TAP( 1.0f,  2.0f, TO);
+#undef LVK_TAP
+    }
+};
+
+// EasuRegrouped (LVK_REMAP_1LSB, opt-in; specification tests/np_easu_1lsb.py): the same 12 taps and the same window, algebraically
+// regrouped -- NOT the reference's operation sequence; every output byte is within 1 of EasuExact's (SURVEY 8c grants the remap <= 1 LSB):
+//   * a tap's distance d2 = |diag(len2) R(dir) off|^2 is a quadratic form in off = (i - ppx, j - ppy): d2 = (q11 ox + 2 q12 oy) ox + q22 oy^2, two
+//     fused multiply-adds per tap over per-row / per-pixel terms instead of rotate (2) + scale (2) + square (2);
+//   * the window (25/16 (2/5 u - 1)^2 - 9/16) (lob u - 1)^2 = ((u / 4 - 5 / 4) u + 1) (lob u - 1)^2: five operations instead of six;
+//   * the taps are accumulated in row order  b c e f g h i j k l n o.
+// (Keeping the colours in 0 .. 255 as well -- 24 more instructions per pixel saved -- is NOT within 1 LSB: up to 22 off where the reference's analysis
+//  amplifies the rounding noise of its own normalisation; built in round 6 and dropped, profiles/r06_ab_remap_tolerant.txt.)
+struct EasuRegrouped
+{
+    static __device__ __forceinline__ void weights(const float4 t[12], float ppx, float ppy, float dirx, float diry, float len2x, float len2y,
+                                                   float lob, float clp, F3& aC, float& aW)
+    {
+        const float a = len2x * dirx, b = len2x * diry, c = len2y * diry, d = len2y * dirx;      // rows of diag(len2) R: (a, b), (-c, d)
+        const float q11 = fma_(a, a, c * c), q22 = fma_(b, b, d * d);
+        const float q12 = fma_(a, b, -(c * d));
+        const float q12x2 = q12 + q12;
+        const float ox[4] = {-1.0f - ppx, 0.0f - ppx, 1.0f - ppx, 2.0f - ppx};
+        // per row J: E = 2 q12 oy and B = q22 oy^2, formed where the row starts (only one row's pair is live at a time: the 4:2:0 mesh kernels
+        // hold 80 VGPRs with them and 81 with all four rows' terms formed up front)
+#define LVK_ROW(J) const float oy##J = (float)(J - 1) - ppy, E##J = q12x2 * oy##J, B##J = (q22 * oy##J) * oy##J;
+#define LVK_TAP(I, J, T)                                                                   \
+        {                                                                                  \
+            const float u = min_(fma_(fma_(q11, ox[I], E##J), ox[I], B##J), clp);          \
+            const float sA = fma_(lob, u, -1.0f);                                          \
+            const float qB = fma_(fma_(u, 0.25f, -1.25f), u, 1.0f);                        \
+            const float w = qB * (sA * sA);                                                \
+            aC.x = fma_(t[T].x, w, aC.x);                                                  \
+            aC.y = fma_(t[T].y, w, aC.y);                                                  \
+            aC.z = fma_(t[T].z, w, aC.z);                                                  \
+            aW += w;                                                                       \
+        }
+        LVK_ROW(0) LVK_TAP(1, 0, TB) LVK_TAP(2, 0, TC)
+        LVK_ROW(1) LVK_TAP(0, 1, TE) LVK_TAP(1, 1, TF) LVK_TAP(2, 1, TG) LVK_TAP(3, 1, TH_)
+        LVK_ROW(2) LVK_TAP(0, 2, TI) LVK_TAP(1, 2, TJ) LVK_TAP(2, 2, TK) LVK_TAP(3, 2, TL)
+        LVK_ROW(3) LVK_TAP(1, 3, TN) LVK_TAP(2, 3, TO)
+#undef LVK_ROW
+#undef LVK_TAP
+    }
+};
+
+// FSR.cl:181-318 on the 12 taps; W = the weight stage.  Returns 0x00ZZYYXX.
+template <class W = EasuExact>
 __device__ __forceinline__ uint32_t easu_core(const float4 t[12], float ppx, float ppy)
 {
     // FSR.cl:244-249
@@ -184,75 +241,10 @@ __device__ __forceinline__ uint32_t easu_core(const float4 t[12], float ppx, flo
     const F3 mi4{ min_(f.x, min_(g.x, min_(j.x, k.x))), min_(f.y, min_(g.y, min_(j.y, k.y))), min_(f.z, min_(g.z, min_(j.z, k.z))) };
     const F3 ma4{ max_(f.x, max_(g.x, max_(j.x, k.x))), max_(f.y, max_(g.y, max_(j.y, k.y))), max_(f.z, max_(g.z, max_(j.z, k.z))) };
 
-#ifdef LVK_EASU_TOLERANT
-    // Tolerance-mode A / B partner (SURVEY 8c allows <= 1 LSB / PSNR >= 50 dB for the remap), measured in round 6 and NOT shipped: level 1 (the two regroupings
-    // below) is within 1 LSB everywhere and 6-7 % faster, level 2 (raw colours as well) 10 % faster and up to 22 LSB off where the reference's analysis
-    // amplifies the rounding noise of its own normalisation (profiles/r06_ab_remap_tolerant.txt).  Same 12 taps, same window,
-    // algebraically regrouped -- not the reference's operation sequence:
-    //   * a tap's distance d2 = |diag(len2) R(dir) off|^2 is a quadratic form in off = (i - ppx, j - ppy): d2 = (q11 ox + 2 q12 oy) ox + q22 oy^2, two
-    //     fused multiply-adds per tap over per-row / per-pixel terms instead of rotate (2) + scale (2) + square (2);
-    //   * the window (25/16 (2/5 u - 1)^2 - 9/16) (lob u - 1)^2 = ((u / 4 - 5 / 4) u + 1) (lob u - 1)^2: five operations instead of six;
-    //   * the colours stay in 0 .. 255 (36 normalising multiplies fewer, 12 for the luma more); the closing x 255 becomes x (norm_factor x 255), which
-    //     maps every integer exactly as the reference's round trip does (k -> k - 1 for k >= 1: 0.00392156862f is below 1 / 255).
-    F3 aC{0.0f, 0.0f, 0.0f};
-    float aW = 0.0f;
-    {
-        const float a = len2x * dirx, b = len2x * diry, c = len2y * diry, d = len2y * dirx;      // rows of diag(len2) R: (a, b), (-c, d)
-        const float q11 = fma_(a, a, c * c), q22 = fma_(b, b, d * d);
-        const float q12 = fma_(a, b, -(c * d));
-        const float q12x2 = q12 + q12;
-        const float ox[4] = {-1.0f - ppx, 0.0f - ppx, 1.0f - ppx, 2.0f - ppx};
-        const float oy[4] = {-1.0f - ppy, 0.0f - ppy, 1.0f - ppy, 2.0f - ppy};
-        float E[4], B[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) { E[j] = q12x2 * oy[j]; B[j] = (q22 * oy[j]) * oy[j]; }
-#define LVK_TAP(I, J, T)                                                                   \
-        {                                                                                  \
-            const float u = min_(fma_(fma_(q11, ox[I], E[J]), ox[I], B[J]), clp);          \
-            const float sA = fma_(lob, u, -1.0f);                                          \
-            const float qB = fma_(fma_(u, 0.25f, -1.25f), u, 1.0f);                        \
-            const float w = qB * (sA * sA);                                                \
-            aC.x = fma_(t[T].x, w, aC.x);                                                  \
-            aC.y = fma_(t[T].y, w, aC.y);                                                  \
-            aC.z = fma_(t[T].z, w, aC.z);                                                  \
-            aW += w;                                                                       \
-        }
-        LVK_TAP(1, 0, TB) LVK_TAP(2, 0, TC)
-        LVK_TAP(0, 1, TE) LVK_TAP(1, 1, TF) LVK_TAP(2, 1, TG) LVK_TAP(3, 1, TH_)
-        LVK_TAP(0, 2, TI) LVK_TAP(1, 2, TJ) LVK_TAP(2, 2, TK) LVK_TAP(3, 2, TL)
-        LVK_TAP(1, 3, TN) LVK_TAP(2, 3, TO)
-#undef LVK_TAP
-    }
-    const float rW = rcp_native(aW);
-#if LVK_EASU_TOLERANT >= 2
-    const float out_scale = 0.99999994f;            // float(0.00392156862f * 255): trunc(k * out_scale) == trunc((k * norm_factor) * 255) for every byte k
-#else
-    const float out_scale = 255.0f;                 // level 1: the taps are normalised as in the reference
-#endif
-    const float px = clamp3_(aC.x * rW, mi4.x, ma4.x);
-    const float py = clamp3_(aC.y * rW, mi4.y, ma4.y);
-    const float pz = clamp3_(aC.z * rW, mi4.z, ma4.z);
-    const uint32_t ux = (uint32_t)(int)(px * out_scale) & 0xffu;
-    const uint32_t uy = (uint32_t)(int)(py * out_scale) & 0xffu;
-    const uint32_t uz = (uint32_t)(int)(pz * out_scale) & 0xffu;
-#else
     // FSR.cl:299-313
     F3 aC{0.0f, 0.0f, 0.0f};
     float aW = 0.0f;
-#define LVK_TAP(ox, oy, T) tap(aC, aW, (ox) - ppx, (oy) - ppy, dirx, diry, len2x, len2y, lob, clp, F3{t[T].x, t[T].y, t[T].z})
-    LVK_TAP( 0.0f, -1.0f, TB);
-    LVK_TAP( 1.0f, -1.0f, TC);
-    LVK_TAP(-1.0f,  1.0f, TI);
-    LVK_TAP( 0.0f,  1.0f, TJ);
-    LVK_TAP( 0.0f,  0.0f, TF);
-    LVK_TAP(-1.0f,  0.0f, TE);
-    LVK_TAP( 1.0f,  1.0f, TK);
-    LVK_TAP( 2.0f,  1.0f, TL);
-    LVK_TAP( 2.0f,  0.0f, TH_);
-    LVK_TAP( 1.0f,  0.0f, TG);
-    LVK_TAP( 0.0f,  2.0f, TN);
-    LVK_TAP( 1.0f,  2.0f, TO);
-#undef LVK_TAP
+    W::weights(t, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, aC, aW);
 
     // FSR.cl:316-317
     // aW: the centre taps alone contribute > 0.5 and no tap reaches 2, so 1/aW and aW are normal numbers
@@ -264,7 +256,6 @@ __device__ __forceinline__ uint32_t easu_core(const float4 t[12], float ppx, flo
     const uint32_t ux = (uint32_t)(int)(px * 255.0f) & 0xffu;
     const uint32_t uy = (uint32_t)(int)(py * 255.0f) & 0xffu;
     const uint32_t uz = (uint32_t)(int)(pz * 255.0f) & 0xffu;
-#endif
     return ux | (uy << 8) | (uz << 16);
 }
 
@@ -279,7 +270,7 @@ __device__ __forceinline__ TapBases tap_bases(const uint8_t* __restrict__ src, i
     return TapBases{src, src + step - 3, src + 2 * (long)step - 3, src + 3 * (long)step};
 }
 
-template <bool YUV>
+template <bool YUV, class W = EasuExact>
 __device__ __forceinline__ uint32_t easu_gather(const TapBases& tb, int step, int sx, int sy, float ppx, float ppy)
 {
     // sy >= 1, sx >= 1 here (interior pixels only): the offset of tap b (row sy - 1, column sx) is non-negative
@@ -296,7 +287,7 @@ __device__ __forceinline__ uint32_t easu_gather(const TapBases& tb, int step, in
     t[TI] = make_tap<YUV>(r2.w[0]);                                t[TJ] = make_tap<YUV>(byte_window(r2.w[0], r2.w[1], 3));
     t[TK] = make_tap<YUV>(byte_window(r2.w[1], r2.w[2], 2));       t[TL] = make_tap<YUV>(byte_window(r2.w[2], 0u, 1));
     t[TN] = make_tap<YUV>(r3.w[0]);                                t[TO] = make_tap<YUV>(byte_window(r3.w[0], r3.w[1], 3));
-    return easu_core(t, ppx, ppy);
+    return easu_core<W>(t, ppx, ppy);
 }
 
 // the object at `base` + a 32-bit byte offset (base block-uniform: global_load v, v_off, s[base:base+1])
@@ -539,7 +530,7 @@ struct Sink420
     }
 };
 
-template <bool YUV, class Coord, class Sink>
+template <bool YUV, class W = EasuExact, class Coord, class Sink>
 __device__ __forceinline__ void remap_one_strip(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
                                                 const Sink& sink, int dst_rows, int dst_cols, const Coord& coord, uint32_t bg,
                                                 int strip, int nstrips, int strips_x, int parity)
@@ -576,13 +567,13 @@ __device__ __forceinline__ void remap_one_strip(const uint8_t* __restrict__ src,
                 }
                 else px[p] = bg;
             }
-            else px[p] = easu_gather<YUV>(tb, src_step, sx, sy, ppx, ppy);
+            else px[p] = easu_gather<YUV, W>(tb, src_step, sx, sy, ppx, ppy);
         }
     }
     sink.store(x0, y, npx, px, active, parity);
 }
 
-template <bool YUV, class Coord, class Sink>
+template <bool YUV, class W = EasuExact, class Coord, class Sink>
 __device__ __forceinline__ void remap_strip(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
                                             const Sink& sink, int dst_rows, int dst_cols,
                                             const Coord& coord, uint32_t bg)
@@ -601,9 +592,21 @@ __device__ __forceinline__ void remap_strip(const uint8_t* __restrict__ src, int
     {
         const int strip = xcd * band + k;
         if (strip >= nstrips) break;                                    // block-uniform (only the last band is short)
-        remap_one_strip<YUV>(src, src_step, src_rows, src_cols, sink, dst_rows, dst_cols, coord, bg, strip, nstrips, strips_x, parity);
+        remap_one_strip<YUV, W>(src, src_step, src_rows, src_cols, sink, dst_rows, dst_cols, coord, bg, strip, nstrips, strips_x, parity);
     }
 }
+// Every three-channel remap kernel exists twice, as two __global__ functions with base names of their own and ONE body: NAME runs the
+// EasuExact weight stage (LVK_REMAP_EXACT), NAME_r1 the EasuRegrouped one (LVK_REMAP_1LSB).  Inside the body `W` names the weight stage.
+// TPARAM: the kernel's one template parameter; ATTR: further attributes (LVK_CO_SCHEDULED) or nothing.
+#define LVK_REMAP_KERNEL(TPARAM, ATTR, NAME, PARAMS, ...)                                                                          \
+    template <TPARAM> __global__ __launch_bounds__(256) LVK_REMAP_ATTR ATTR void NAME PARAMS { using W = EasuExact; __VA_ARGS__ }  \
+    template <TPARAM> __global__ __launch_bounds__(256) LVK_REMAP_ATTR ATTR void NAME##_r1 PARAMS { using W = EasuRegrouped; __VA_ARGS__ }
+// ... and, for the kernels the overlap mode launches as a persistent grid, twice more as NAME_co / NAME_co_r1
+#define LVK_REMAP_KERNEL_CO(TPARAM, NAME, PARAMS, ...)                 \
+    LVK_REMAP_KERNEL(TPARAM, , NAME, PARAMS, __VA_ARGS__)              \
+    LVK_REMAP_KERNEL(TPARAM, LVK_CO_SCHEDULED, NAME##_co, PARAMS, __VA_ARGS__)
+inline bool remap_precision_known(int precision) { return precision == LVK_REMAP_EXACT || precision == LVK_REMAP_1LSB; }
+
 inline dim3 remap_grid(int dst_rows, int dst_cols)
 {
     const int nstrips = ((dst_cols + STRIP_W - 1) / STRIP_W) * ((dst_rows + STRIP_H - 1) / STRIP_H);

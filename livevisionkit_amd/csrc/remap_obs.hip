@@ -83,47 +83,50 @@ struct Sink444
     }
 };
 
-template <class Sink>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_homography_planes(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink, HomographyArgs H, uint32_t bg)
+// (each LVK_REMAP_KERNEL below defines the exact kernel NAME and its 1-LSB twin NAME_r1 from one body -- remap_core.hpp)
+LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_homography_planes,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink, HomographyArgs H, uint32_t bg),
 {
-    remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, HomographyCoord{H, 0, 0}, bg);
-}
+    remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, HomographyCoord{H, 0, 0}, bg);
+})
 
-template <class Sink>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_homography_lens_planes(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink, HomographyArgs H, LensArgs L, uint32_t bg)
+LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_homography_lens_planes,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink, HomographyArgs H, LensArgs L, uint32_t bg),
 {
-    remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, LensCoord<HomographyCoord>{HomographyCoord{H, 0, 0}, L, rows, cols}, bg);
-}
+    remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<HomographyCoord>{HomographyCoord{H, 0, 0}, L, rows, cols}, bg);
+})
 
-template <class Sink>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_mesh_planes(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink,
-                         const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg)
+LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_mesh_planes,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink,
+                  const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg),
 {
-    if (mesh_to_lds(mesh, mesh_floats)) remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
-    else remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
-}
+    if (mesh_to_lds(mesh, mesh_floats)) remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
+    else remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
+})
 
-template <class Sink>
-__global__ __launch_bounds__(256) LVK_REMAP_ATTR LVK_CO_SCHEDULED
-void k_remap_mesh_lens_planes(const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink,
-                              const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab,
-                              LensArgs L, uint32_t bg)
+LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_mesh_lens_planes,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink,
+                  const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab,
+                  LensArgs L, uint32_t bg),
 {
     if (mesh_to_lds(mesh, mesh_floats))
-        remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
+        remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
     else
-        remap_strip<true>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
-}
+        remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
+})
 
 template <class Sink>
 int launch_planes(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, const Sink& sink,
-                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const LensArgs* lens, bool co)
+                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const LensArgs* lens, bool co, int precision)
 {
     const dim3 block(256), grid = co ? lvk_co_grid(ctx, rows, cols) : remap_grid(rows, cols);
     int stage_slot = -1;
+    // one launch: the exact kernel or its 1-LSB twin
+#define LVK_LAUNCH_PLANES(K, ...)                                                                                                                              \
+    do {                                                                                                                                                       \
+        if (precision == LVK_REMAP_1LSB) hipLaunchKernelGGL(K##_r1<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, __VA_ARGS__, pack_bg(bg)); \
+        else hipLaunchKernelGGL(K<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, __VA_ARGS__, pack_bg(bg));                  \
+    } while (0)
     if (mesh_rows == 2 && mesh_cols == 2)
     {
         const float w = (float)cols, h = (float)rows;                 // WarpMesh.cpp:194-217, as in lvk_launch_warpmesh_apply_lens
@@ -139,8 +142,8 @@ int launch_planes(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int s
             for (int q = 0; q < 9; q++) M[q] = (q % 4 == 0) ? 1.0 : 0.0;
         HomographyArgs args;
         for (int q = 0; q < 9; q++) args.h[q] = (float)M[q];
-        if (lens) hipLaunchKernelGGL(k_remap_homography_lens_planes<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, args, *lens, pack_bg(bg));
-        else hipLaunchKernelGGL(k_remap_homography_planes<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, args, pack_bg(bg));
+        if (lens) LVK_LAUNCH_PLANES(k_remap_homography_lens_planes, args, *lens);
+        else LVK_LAUNCH_PLANES(k_remap_homography_planes, args);
     }
     else
     {
@@ -152,11 +155,10 @@ int launch_planes(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int s
         if ((rc = lvk_get_lintab(ctx, mesh_rows, rows, true, &ytab)) != LVK_HIP_OK) return rc;
         void* d_mesh = nullptr;
         if ((rc = lvk_stage_params(ctx, stream, mesh, mesh_bytes, &d_mesh, &stage_slot)) != LVK_HIP_OK) return rc;
-        if (lens) hipLaunchKernelGGL(k_remap_mesh_lens_planes<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, (const float*)d_mesh, mesh_cols,
-                                     mesh_rows * mesh_cols * 2, xtab, ytab, *lens, pack_bg(bg));
-        else hipLaunchKernelGGL(k_remap_mesh_planes<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, (const float*)d_mesh, mesh_cols,
-                                mesh_rows * mesh_cols * 2, xtab, ytab, pack_bg(bg));
+        if (lens) LVK_LAUNCH_PLANES(k_remap_mesh_lens_planes, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, *lens);
+        else LVK_LAUNCH_PLANES(k_remap_mesh_planes, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab);
     }
+#undef LVK_LAUNCH_PLANES
     const hipError_t le = hipGetLastError();
     const int src = stage_slot >= 0 ? lvk_stage_consumed(ctx, stage_slot, stream) : LVK_HIP_OK;
     if (le != hipSuccess) return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(le));
@@ -178,8 +180,9 @@ bool lvk_remap_obs_fusable(int video_format)
 // WarpMesh::apply + FrameIngest::to_obs of `video_format` in one kernel; the planes' geometry has been checked by the caller (lvk_stab_push_planes).
 int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format, const void* d_src, int src_step, int rows, int cols,
                                   void* const planes[3], const int steps[3], const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3],
-                                  const LensArgs* lens, bool co)
+                                  const LensArgs* lens, bool co, int precision)
 {
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(precision));
     LVK_HIP_REQUIRE(ctx, d_src && planes && steps && planes[0] && mesh && bg && mesh_rows >= 2 && mesh_cols >= 2 && rows > 0 && cols > 0 && src_step >= 3 * cols);
     LVK_HIP_REQUIRE(ctx, fits_u32(src_step, rows) && fits_u32(steps[0], rows));
     uint8_t* p0 = (uint8_t*)planes[0]; uint8_t* p1 = (uint8_t*)planes[1]; uint8_t* p2 = (uint8_t*)planes[2];
@@ -189,22 +192,22 @@ int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, hipStream_t stream, int vide
     {
     case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A:
         LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= cols && steps[1] >= cols / 2 && steps[2] >= cols / 2);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, lens, co);
+        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
     case LVK_VIDEO_FORMAT_YUY2:
         LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co);
+        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
     case LVK_VIDEO_FORMAT_YVYU:
         LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<2>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co);
+        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<2>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
     case LVK_VIDEO_FORMAT_UYVY:
         LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<3>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co);
+        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<3>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
     case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA:
         LVK_HIP_REQUIRE(ctx, steps[0] >= cols && steps[1] >= cols && steps[2] >= cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink444<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, lens, co);
+        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink444<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
     case LVK_VIDEO_FORMAT_AYUV:
         LVK_HIP_REQUIRE(ctx, steps[0] >= 4 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink444<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co);
+        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink444<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
     }
     return ctx->fail(LVK_HIP_ERR_ARG, "lvk_launch_warpmesh_apply_obs: no fused sink for video format " + std::to_string(video_format));
 }

@@ -434,6 +434,19 @@ int lvk_hip_stab_set_bulk_context(lvk_hip_stab* st, lvk_hip_ctx* bulk)
     return stab_set_overlap(st, bulk != nullptr, bulk);
 }
 
+// The kernels of the three-channel output remap from the next emitted frame on: LVK_REMAP_EXACT (the default) or LVK_REMAP_1LSB (remap_core.hpp,
+// EasuRegrouped).  Only the field changes -- emit() reads it at its launch --: no stream is waited for, the queue, the trajectory and the tracker stay.
+int lvk_hip_stab_set_remap_precision(lvk_hip_stab* st, int precision)
+{
+    if (!st) return LVK_HIP_ERR_ARG;
+    if (precision != LVK_REMAP_EXACT && precision != LVK_REMAP_1LSB)
+        return st->ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_set_remap_precision: unknown precision " + std::to_string(precision));
+    st->remap_precision = precision;
+    return LVK_HIP_OK;
+}
+
+int lvk_hip_stab_get_remap_precision(const lvk_hip_stab* st) { return st ? st->remap_precision : LVK_HIP_ERR_ARG; }
+
 // Per-stage GPU time measured with HIP events on the launch stream.  enable != 0 starts (and resets) the
 // accumulation; lvk_hip_stab_get_profile synchronises the stream and reports, per stage, the summed milliseconds
 // and the number of timed launches (stage ids: LVK_STAGE_*).

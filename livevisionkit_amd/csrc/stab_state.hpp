@@ -184,6 +184,10 @@ struct lvk_hip_stab
     double last_H[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     WarpMeshF last_motion, last_correction;
 
+    // lvk_hip_stab_set_remap_precision: the kernels of the three-channel output remap, read by emit() at every launch (the GRAY remap is exact in both);
+    // a stabilizer is created EXACT whatever its context's setting
+    int remap_precision = LVK_REMAP_EXACT;
+
     // ---- optional overlap of the output remap with the next frame's tracking (second stream)
     bool overlap = false;
     hipStream_t remap_stream = nullptr;

@@ -472,19 +472,19 @@ int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows
         }
         if (mesh && o420 && o420->y && o420->vf != 0)
         {
-            rc = lvk_launch_warpmesh_apply_obs(ctx, rs, o420->vf, f.d_ptr, f.step, f.rows, f.cols, o420->p, o420->s, mesh->off.data(), mesh->rows, mesh->cols, bg, lens_args, persistent);
+            rc = lvk_launch_warpmesh_apply_obs(ctx, rs, o420->vf, f.d_ptr, f.step, f.rows, f.cols, o420->p, o420->s, mesh->off.data(), mesh->rows, mesh->cols, bg, lens_args, persistent, st->remap_precision);
             o420->used = true;
         }
         else if (mesh && o420 && o420->y)
         {
             rc = lvk_launch_warpmesh_apply_420(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, o420->y, o420->y_step, o420->u, o420->u_step, o420->v, o420->v_step,
-                                               o420->nv12, mesh->off.data(), mesh->rows, mesh->cols, bg, lens_args, persistent);
+                                               o420->nv12, mesh->off.data(), mesh->rows, mesh->cols, bg, lens_args, persistent, st->remap_precision);
             o420->used = true;
         }
         else if (mesh && gray_entry) rc = lvk_launch_warpmesh_apply_lens_gray(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg[0],
                                                                               lens_args, persistent);
         else if (mesh) rc = lvk_launch_warpmesh_apply_lens(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg,
-                                                      f.format == LVK_FORMAT_YUV ? 1 : 0, lens_args, persistent);
+                                                      f.format == LVK_FORMAT_YUV ? 1 : 0, lens_args, persistent, st->remap_precision);
         else
         {
             hipError_t e = hipMemcpy2DAsync(d_out, out_step, f.d_ptr, f.step, (size_t)f.cols * bpp, f.rows, hipMemcpyDeviceToDevice, ctx->stream);

@@ -8,7 +8,7 @@ import time
 import numpy as np
 
 from . import _native
-from .context import Context
+from .context import Context, _remap_precision
 
 _c = ctypes
 
@@ -496,6 +496,15 @@ class StabilizationFilter:
     def set_overlap(self, enable=True):
         """Run the output remap on a second stream, overlapping the next frame's tracking (output valid after ctx.sync())."""
         self.ctx._check(self.lib.lvk_hip_stab_set_overlap(self.handle, 1 if enable else 0))
+
+    def set_remap_precision(self, precision):
+        """REMAP_EXACT (default) or REMAP_1LSB for this filter's output remap, from the next emitted frame on: nothing restarts, the queue and the
+        trajectory are kept.  A filter is created exact whatever its context's setting; GRAY frames stay exact in both."""
+        self.ctx._check(self.lib.lvk_hip_stab_set_remap_precision(self.handle, _remap_precision(precision)))
+
+    @property
+    def remap_precision(self):
+        return self.lib.lvk_hip_stab_get_remap_precision(self.handle)
 
     STAGES = ("downscale", "pyramid", "fast", "pyrlk", "motion", "remap", "ingest", "egress")
 
