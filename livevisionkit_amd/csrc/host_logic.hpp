@@ -1,9 +1,10 @@
-// Host-side state machines of the stabilization path (no device code): warp-mesh arithmetic, the path
-// smoother, and the feature detector's suppression grid / region bookkeeping.  These are tiny (<= a few
+// Host-side state machines of the stabilization path (no device code): warp-mesh arithmetic, the 2 x 2 mesh's
+// homography, the path smoother, and the feature detector's suppression grid / region bookkeeping.  These are tiny (<= a few
 // thousand elements per frame) and inherently sequential, so they stay on the host exactly as in the reference.
 //
 // Reference (paths relative to LiveVisionKit/):
 //   Math/WarpMesh.cpp:318-551, Math/Homography.cpp:125-130         -> WarpMeshF
+//   Math/WarpMesh.cpp:194-217 (+ cv::getPerspectiveTransform)       -> mesh2x2_to_homography, perspective_transform
 //   Vision/PathSmoother.cpp:36-145, Functions/Logic.tpp:53-65       -> PathSmootherH
 //   Vision/FeatureDetector.cpp:48-214, Data/SpatialMap.tpp:589-625  -> FeatureGridH
 // Elementwise float ops follow OpenCV's scalar definitions: one rounding per op, no contraction.
@@ -28,6 +29,66 @@ struct Feature { float x, y, response; int age; };          // cv::KeyPoint {pt,
 // ------------------------------------------------------------------------------------------------ WarpMesh
 // (shared with the C++ facade's lvk::WarpMesh: include/lvk/WarpMeshCore.hpp)
 using WarpMeshF = lvk::detail::WarpMeshF;
+
+// cv::getPerspectiveTransform (OpenCV 4.8 imgproc; call site Math/WarpMesh.cpp:214): 8x8 double system,
+// LU with partial pivoting.  Maps src[i] -> dst[i].
+inline bool perspective_transform(const float src[8], const float dst[8], double M[9])
+{
+    double A[8][8], B[8];
+    for (int i = 0; i < 4; i++)
+    {
+        const double x = src[2 * i], y = src[2 * i + 1], u = dst[2 * i], v = dst[2 * i + 1];
+        A[i][0] = A[i + 4][3] = x;  A[i][1] = A[i + 4][4] = y;  A[i][2] = A[i + 4][5] = 1.0;
+        A[i][3] = A[i][4] = A[i][5] = A[i + 4][0] = A[i + 4][1] = A[i + 4][2] = 0.0;
+        A[i][6] = -x * u;  A[i][7] = -y * u;  A[i + 4][6] = -x * v;  A[i + 4][7] = -y * v;
+        B[i] = u;  B[i + 4] = v;
+    }
+    for (int i = 0; i < 8; i++)
+    {
+        int piv = i;
+        for (int j = i + 1; j < 8; j++) if (std::fabs(A[j][i]) > std::fabs(A[piv][i])) piv = j;
+        if (std::fabs(A[piv][i]) < 2.220446049250313e-16 * 100) return false;
+        if (piv != i) { for (int j = i; j < 8; j++) std::swap(A[i][j], A[piv][j]); std::swap(B[i], B[piv]); }
+        const double d = -1.0 / A[i][i];
+        for (int j = i + 1; j < 8; j++)
+        {
+            const double alpha = A[j][i] * d;
+            for (int q = i + 1; q < 8; q++) A[j][q] += alpha * A[i][q];
+            B[j] += alpha * B[i];
+        }
+    }
+    for (int i = 7; i >= 0; i--)
+    {
+        double s = B[i];
+        for (int q = i + 1; q < 8; q++) s -= A[i][q] * B[q];
+        B[i] = s / A[i][i];
+    }
+    for (int q = 0; q < 8; q++) M[q] = B[q];
+    M[8] = 1.0;
+    return true;
+}
+
+// WarpMesh::apply of a 2 x 2 mesh (WarpMesh.cpp:194-217): the frame's corners displaced by offsets * (cols, rows), then
+// getPerspectiveTransform(destination, source) -- the identity where that fails -- cast to binary32 (Image.cpp:137-139).  The one place every
+// remap launcher (packed, 4:2:0, the other OBS sinks, one-channel) takes this route from.
+inline void mesh2x2_to_homography(const float mesh[8], int rows, int cols, float H[9])
+{
+    const float w = (float)cols, h = (float)rows;
+    const float dstp[8] = { 0, 0, w, 0, 0, h, w, h };
+    float srcp[8];
+    for (int i = 0; i < 4; i++)
+    {
+        // Point2f * Scalar: float * double, rounded back to float (Functions/Extensions.cpp operator*(Point2f, Scalar))
+        const float mx = (float)((double)mesh[2 * i] * (double)cols);
+        const float my = (float)((double)mesh[2 * i + 1] * (double)rows);
+        srcp[2 * i] = dstp[2 * i] + mx;
+        srcp[2 * i + 1] = dstp[2 * i + 1] + my;
+    }
+    double M[9];
+    if (!perspective_transform(dstp, srcp, M))
+        for (int q = 0; q < 9; q++) M[q] = (q % 4 == 0) ? 1.0 : 0.0;
+    for (int q = 0; q < 9; q++) H[q] = (float)M[q];
+}
 
 // ------------------------------------------------------------------------------------------------ PathSmoother
 class PathSmootherH

@@ -27,7 +27,6 @@ struct PyrArgs { PyrLevel lv[LVK_MAX_PYR_LEVELS]; int nlevels; };
 struct lvk_hip_ctx
 {
     int remap_precision = LVK_REMAP_EXACT;  // lvk_hip_set_remap_precision: the kernels of the stateless three-channel remap entries (a stabilizer has its own)
-    int co_blocks_per_cu = 0;               // persistent remap grid of the overlap mode: blocks per CU for the next launch (0: the default)
     int device = 0;
     int cu_count = 0;                   // compute units of the device (persistent-grid sizing of the remap)
     hipStream_t stream = nullptr;
@@ -313,17 +312,24 @@ struct LvkTrackChain
 int lvk_launch_track_chain(lvk_hip_ctx* ctx, const LvkTrackChain& c);
 
 struct LensArgs;
-// Dense remap on an explicit stream (remap.hip).  precision: LVK_REMAP_EXACT or LVK_REMAP_1LSB -- it selects the kernel of the ONE launch (the exact
-// kernel or its `_r1` twin); any other value is refused.  The caller decides where it comes from: the context's setting for the stateless entries,
-// the stabilizer's own for its emits.
-int lvk_launch_remap_homography(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
+// How a dense remap is launched: the last argument of every lvk_launch_remap_* / lvk_launch_warpmesh_apply_* below.
+struct RemapLaunch
+{
+    hipStream_t stream = nullptr;
+    // LVK_REMAP_EXACT or LVK_REMAP_1LSB -- it selects the kernel of the ONE launch (the exact kernel or its `_r1` twin); any other value is refused.  The
+    // caller decides where it comes from: the context's setting for the stateless entries, the stabilizer's own for its emits.  The one-channel kernels
+    // have no twin and do not look at it.
+    int precision = LVK_REMAP_EXACT;
+    const LensArgs* lens = nullptr;     // != nullptr composes the closed-form lens map into the coordinate (fused mode)
+    bool co_scheduled = false;          // overlap mode: the persistent grid (and, for the packed kernels, their `_co` forms) ...
+    int co_blocks_per_cu = 0;           // ... of this many blocks per CU: 0 = the default, k > 0 = k blocks per CU, -k = one block per k CUs
+};
+// Dense remap (remap.hip)
+int lvk_launch_remap_homography(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
                                 void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y,
-                                const float H[9], const uint8_t bg[3], int yuv, const LensArgs* lens, bool co_scheduled, int precision);
-int lvk_launch_remap_mesh(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
-                          void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv,
-                          const LensArgs* lens, bool co_scheduled, int precision);
-int lvk_launch_warpmesh_apply(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                              void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, int precision);
+                                const float H[9], const uint8_t bg[3], int yuv, const RemapLaunch& o);
+int lvk_launch_remap_mesh(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
+                          void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const RemapLaunch& o);
 
 // YUV420 <-> packed 444 (ingest.hip)
 int lvk_launch_ingest_yuv420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_y, int y_step, const void* d_u, int u_step,
@@ -337,8 +343,8 @@ int lvk_launch_egress_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format
                           void* const d_planes[3], const int steps[3]);
 
 
-int lvk_launch_remap_map(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                         void* d_dst, int dst_step, const void* d_map, int map_step, const uint8_t bg[3], int yuv, int precision);
+int lvk_launch_remap_map(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
+                         void* d_dst, int dst_step, const void* d_map, int map_step, const uint8_t bg[3], int yuv, const RemapLaunch& o);   // no lens, full grid
 
 // Fused lens pre-warp (lens.hip): the camera profile reduced to what the closed-form map needs for one frame size.
 // d = nfx, nfy, ncx, ncy (new camera matrix), fx, fy, cx, cy, k1, k2, p1, p2, k3, kxc, vxc, kyc, vyc (crop_in term, pixels);
@@ -378,21 +384,19 @@ int lvk_lens_model_build(const lvk_camera_params& params, int rows, int cols, Le
 // (a | b)[i] raw tracking-frame points -> lens-corrected positions, binary64, written to out[0 .. na + nb)
 int lvk_launch_lens_undistort(lvk_hip_ctx* ctx, hipStream_t stream, const LensModel& model, double sx, double sy,
                               const float2* a, int na, const float2* b, int nb, float2* out);
-// lens != nullptr composes the closed-form lens map into the coordinate (fused mode)
-int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                                   void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv,
-                                   const LensArgs* lens, bool co_scheduled, int precision);   // co_scheduled: occupancy-capped kernels for overlap mode
+// WarpMesh::apply: a 2 x 2 mesh through lvkh::mesh2x2_to_homography and the homography kernel, anything larger through the mesh kernel
+int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
+                                   void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const RemapLaunch& o);
 
 // Dense remap of one-channel (8UC1) frames (remap_gray.hip): channel 0 of the non-YUV EASU program on (g, c, c); bg = the background byte
-int lvk_launch_remap_homography_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
-                                     void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y,
-                                     const float H[9], uint8_t bg, const LensArgs* lens = nullptr, bool co_scheduled = false);
-int lvk_launch_remap_mesh_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
-                               const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const LensArgs* lens = nullptr, bool co_scheduled = false);
-int lvk_launch_remap_map_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                              void* d_dst, int dst_step, const void* d_map, int map_step, uint8_t bg);
-int lvk_launch_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
-                                        const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const LensArgs* lens, bool co_scheduled = false);   // co_scheduled: the persistent grid of the overlap mode (same kernel body)
+int lvk_launch_remap_homography_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
+                                     void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], uint8_t bg, const RemapLaunch& o);
+int lvk_launch_remap_mesh_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                               const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const RemapLaunch& o);
+int lvk_launch_remap_map_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
+                              void* d_dst, int dst_step, const void* d_map, int map_step, uint8_t bg, const RemapLaunch& o);   // no lens, full grid
+int lvk_launch_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                                        const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const RemapLaunch& o);
 
 // Debug overlays (draw.hip)
 int lvk_launch_draw_grid(lvk_hip_ctx* ctx, hipStream_t stream, void* d_dst, int dst_step, int rows, int cols, int grid_w, int grid_h,
@@ -418,11 +422,9 @@ int lvk_launch_mesh_solve(lvk_mesh_solver_dev* s, hipStream_t stream, void* d_sc
                           float* h_offsets, uint8_t* h_mask, int* h_status);
 
 // remap + 4:2:0 egress in one kernel (remap.hip)
-int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
+int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
                                   void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int nv12,
-                                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const LensArgs* lens,
-                                  bool co_scheduled, int precision);
+                                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const RemapLaunch& o);
 bool lvk_remap_obs_fusable(int video_format);
-int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format, const void* d_src, int src_step, int rows, int cols,
-                                  void* const planes[3], const int steps[3], const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3],
-                                  const LensArgs* lens, bool co, int precision);          // co_scheduled: the persistent grid of the overlap mode
+int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, int video_format, const void* d_src, int src_step, int rows, int cols,
+                                  void* const planes[3], const int steps[3], const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const RemapLaunch& o);

@@ -1,5 +1,9 @@
-// (remap_core.hpp: the device code and host helpers shared by remap.hip -- the packed and 4:2:0 kernels and their launchers -- and remap_obs.hip -- the
-//  fused remap + egress kernels of the other OBS video formats.  Everything lives in an anonymous namespace: each translation unit has its own copy.)
+// (remap_core.hpp: the device code and host helpers shared by remap.hip -- the packed and 4:2:0 kernels and their launchers --, remap_obs.hip -- the
+//  fused remap + egress kernels of the other OBS video formats -- and remap_gray.hip.  Everything lives in an anonymous namespace: each translation unit
+//  has its own copy.  Device side: EASU, the coordinate functors and their builders (lens_coord, with_homography_coord, LVK_WITH_MESH_COORD), the sinks, the
+//  strip walk (walk_strips) and the homography kernels' body remap_homography.  Host side, at the end: the kernel-defining macros with the table of a family's
+//  forms and the one launch (launch_remap), the grids, the argument rules, and the mesh staging protocol (with_staged_mesh).  The 2 x 2 mesh route is
+//  lvkh::mesh2x2_to_homography in host_logic.hpp.)
 //
 // Dense frame remap for gfx950: the EASU (edge adaptive, 12-tap) resampler driven either by a 3x3
 // homography or by a warp mesh that is interpolated inside the kernel.
@@ -19,11 +23,13 @@
 // dwordx2/x4 loads, XCD-aware strip order.
 #pragma once
 #include "lvk_hip_internal.hpp"
+#include "host_logic.hpp"
 
 #include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -410,6 +416,30 @@ struct LensCoord
     }
 };
 
+// ---- coordinate builders: every homography and mesh kernel gets its functor from with_homography_coord or LVK_WITH_MESH_COORD --------------------------
+// LENS: the coordinate is wrapped in the lens pre-warp L of a rows x cols frame (L is not read without it)
+template <bool LENS, class Coord>
+__device__ __forceinline__ auto lens_coord(const Coord& coord, const LensArgs& L, int rows, int cols)
+{
+    if constexpr (LENS) return LensCoord<Coord>{coord, L, rows, cols};
+    else return coord;
+}
+
+template <bool LENS, class F>
+__device__ __forceinline__ void with_homography_coord(const HomographyArgs& H, int off_x, int off_y, const LensArgs& L, int rows, int cols, const F& f)
+{
+    f(lens_coord<LENS>(HomographyCoord{H, off_x, off_y}, L, rows, cols));
+}
+
+// The mesh of a ROWS x COLS frame: staged in LDS by this block where it fits (mesh_to_lds), read from global memory otherwise; RUN is the statement that
+// runs the strips with `coord`, once per arm.  Expanded in the body of a kernel whose parameters are named mesh, mesh_cols, mesh_floats, xtab, ytab; L: the
+// kernel's LensArgs, or LensArgs{} for LENS = false.  A macro and not a function that takes a callable: the block's fill loop and barrier have to stand
+// in the __global__ function itself -- behind any function of its own, forced inline or not, the compiler carries block-uniform values of the strip walk
+// through that loop in vector registers (6 VGPRs and some 40 VALU instructions more in every mesh kernel).
+#define LVK_WITH_MESH_COORD(LENS, L, ROWS, COLS, RUN)                                                                                                        \
+    if (mesh_to_lds(mesh, mesh_floats)) { const auto coord = lens_coord<LENS>(MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)(COLS), (float)(ROWS)}, L, ROWS, COLS); RUN; }  \
+    else { const auto coord = lens_coord<LENS>(MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)(COLS), (float)(ROWS)}, L, ROWS, COLS); RUN; }
+
 // ---- kernel body ---------------------------------------------------------------------------------------------------
 // rocprofv3 (profiles/r06_remap_stalls.txt: the SQ_* / GRBM counters of THIS kernel, round 6) shows it is VALU-issue bound, not memory bound:
 // 488 VALU instructions per output pixel, one leaving each SIMD every 2.94 cycles (0.68 of the 2-cycle issue slots; 0.85 of what its mix of
@@ -573,12 +603,12 @@ __device__ __forceinline__ void remap_one_strip(const uint8_t* __restrict__ src,
     sink.store(x0, y, npx, px, active, parity);
 }
 
-template <bool YUV, class W = EasuExact, class Coord, class Sink>
-__device__ __forceinline__ void remap_strip(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
-                                            const Sink& sink, int dst_rows, int dst_cols,
-                                            const Coord& coord, uint32_t bg)
+// The strip walk: `span_cols` x `dst_rows` output pixels cut into STRIP_W x STRIP_H strips, one_strip(strip, nstrips, strips_x, parity) for each strip
+// of this block (parity alternates per strip of a block: Sink420's two buffers).
+template <class F>
+__device__ __forceinline__ void walk_strips(int dst_rows, int span_cols, const F& one_strip)
 {
-    const int strips_x = (dst_cols + STRIP_W - 1) / STRIP_W, strips_y = (dst_rows + STRIP_H - 1) / STRIP_H;
+    const int strips_x = (span_cols + STRIP_W - 1) / STRIP_W, strips_y = (dst_rows + STRIP_H - 1) / STRIP_H;
     const int nstrips = strips_x * strips_y;
     const int band = (nstrips + NUM_XCD - 1) / NUM_XCD;
     // A block walks the band of its XCD with the stride of the launch: one strip per block for a full grid, several for the persistent
@@ -592,9 +622,31 @@ __device__ __forceinline__ void remap_strip(const uint8_t* __restrict__ src, int
     {
         const int strip = xcd * band + k;
         if (strip >= nstrips) break;                                    // block-uniform (only the last band is short)
-        remap_one_strip<YUV, W>(src, src_step, src_rows, src_cols, sink, dst_rows, dst_cols, coord, bg, strip, nstrips, strips_x, parity);
+        one_strip(strip, nstrips, strips_x, parity);
     }
 }
+
+template <bool YUV, class W = EasuExact, class Coord, class Sink>
+__device__ __forceinline__ void remap_strip(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
+                                            const Sink& sink, int dst_rows, int dst_cols,
+                                            const Coord& coord, uint32_t bg)
+{
+    walk_strips(dst_rows, dst_cols, [&](int strip, int nstrips, int strips_x, int parity) __attribute__((always_inline)) {
+        remap_one_strip<YUV, W>(src, src_step, src_rows, src_cols, sink, dst_rows, dst_cols, coord, bg, strip, nstrips, strips_x, parity);
+    });
+}
+
+// The body of the three-channel homography kernels, whatever their sink (remap.hip, remap_obs.hip): the `_lens` kernels are LENS = true of the same
+// source.  (The mesh kernels' shared body is LVK_WITH_MESH_COORD above; they remap a frame onto one of its own size.)
+template <bool YUV, class W, bool LENS, class Sink>
+__device__ __forceinline__ void remap_homography(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols, const Sink& sink, int dst_rows, int dst_cols,
+                                                 int off_x, int off_y, const HomographyArgs& H, const LensArgs& L, uint32_t bg)
+{
+    with_homography_coord<LENS>(H, off_x, off_y, L, src_rows, src_cols, [&](const auto& coord) __attribute__((always_inline)) {
+        remap_strip<YUV, W>(src, src_step, src_rows, src_cols, sink, dst_rows, dst_cols, coord, bg);
+    });
+}
+
 // Every three-channel remap kernel exists twice, as two __global__ functions with base names of their own and ONE body: NAME runs the
 // EasuExact weight stage (LVK_REMAP_EXACT), NAME_r1 the EasuRegrouped one (LVK_REMAP_1LSB).  Inside the body `W` names the weight stage.
 // TPARAM: the kernel's one template parameter; ATTR: further attributes (LVK_CO_SCHEDULED) or nothing.
@@ -605,7 +657,14 @@ __device__ __forceinline__ void remap_strip(const uint8_t* __restrict__ src, int
 #define LVK_REMAP_KERNEL_CO(TPARAM, NAME, PARAMS, ...)                 \
     LVK_REMAP_KERNEL(TPARAM, , NAME, PARAMS, __VA_ARGS__)              \
     LVK_REMAP_KERNEL(TPARAM, LVK_CO_SCHEDULED, NAME##_co, PARAMS, __VA_ARGS__)
-inline bool remap_precision_known(int precision) { return precision == LVK_REMAP_EXACT || precision == LVK_REMAP_1LSB; }
+// The host side of the two macros above: every form of kernel family K as launch_remap() picks from them, [persistent grid][1-LSB][flag].  F0 / F1: the
+// template argument for flag = false / true.  LVK_REMAP_FORMS: a family defined with LVK_REMAP_KERNEL (one kernel serves both grids), LVK_REMAP_FORMS_CO:
+// one defined with LVK_REMAP_KERNEL_CO.
+template <class K> struct RemapForms { K k[2][2][2]; };
+#define LVK_REMAP_FORMS_(K, KCO, F0, F1) \
+    RemapForms<decltype(&K<F0>)>{ { { { K<F0>, K<F1> }, { K##_r1<F0>, K##_r1<F1> } }, { { KCO<F0>, KCO<F1> }, { KCO##_r1<F0>, KCO##_r1<F1> } } } }
+#define LVK_REMAP_FORMS(K, F0, F1) LVK_REMAP_FORMS_(K, K, F0, F1)
+#define LVK_REMAP_FORMS_CO(K, F0, F1) LVK_REMAP_FORMS_(K, K##_co, F0, F1)
 
 inline dim3 remap_grid(int dst_rows, int dst_cols)
 {
@@ -614,59 +673,69 @@ inline dim3 remap_grid(int dst_rows, int dst_cols)
 }
 
 // Persistent grid of the overlap mode: LVK_CO_WAVES blocks (of 4 waves, one per SIMD) per CU, a multiple of the XCD count.
-inline dim3 lvk_co_grid(lvk_hip_ctx* ctx, int dst_rows, int dst_cols)
+// blocks_per_cu (RemapLaunch::co_blocks_per_cu): 0 = that default, k > 0 = k blocks per CU, -k = one block per k CUs
+inline dim3 lvk_co_grid(const lvk_hip_ctx* ctx, int blocks_per_cu, int dst_rows, int dst_cols)
 {
     const int n = ctx->cu_count > 0 ? ctx->cu_count : 256;      // read once per context (no process-wide cache: filters run on many threads)
     const unsigned full = remap_grid(dst_rows, dst_cols).x;
-    // co_blocks_per_cu: k > 0 = k blocks per CU, -k = one block per k CUs (a remap whose stores cross the host link does not need the chip)
-    const int per_cu = ctx->co_blocks_per_cu != 0 ? ctx->co_blocks_per_cu : LVK_CO_WAVES;
+    const int per_cu = blocks_per_cu != 0 ? blocks_per_cu : LVK_CO_WAVES;
     const unsigned persistent = (unsigned)std::max(NUM_XCD, ((per_cu > 0 ? n * per_cu : n / -per_cu) / NUM_XCD) * NUM_XCD);
     return dim3(full < persistent ? full : persistent);
 }
+
+// THE launch of a remap kernel: the form of the family is chosen by (o.co_scheduled, o.precision, flag) and runs over dst_rows x span_cols output pixels
+// on the full grid or the persistent one.  The caller looks at hipGetLastError().
+template <class K, class... Args>
+inline void launch_remap(const lvk_hip_ctx* ctx, const RemapForms<K>& forms, bool flag, int dst_rows, int span_cols, const RemapLaunch& o, size_t lds_bytes,
+                         const Args&... args)
+{
+    const dim3 grid = o.co_scheduled ? lvk_co_grid(ctx, o.co_blocks_per_cu, dst_rows, span_cols) : remap_grid(dst_rows, span_cols);
+    hipLaunchKernelGGL(forms.k[o.co_scheduled ? 1 : 0][o.precision == LVK_REMAP_1LSB ? 1 : 0][flag ? 1 : 0], grid, dim3(256), lds_bytes, o.stream, args...);
+}
+
+// ---- argument rules shared by the launchers, once each ------------------------------------------------------------------------------------------
+inline bool remap_precision_known(int precision) { return precision == LVK_REMAP_EXACT || precision == LVK_REMAP_1LSB; }
 
 // The kernels address a frame with ONE 32-bit byte offset per pixel built from 24-bit factors (easu_gather, the sinks): the whole frame
 // must lie within 4 GB of its base and rows / pitch below 2^24 (an 8K packed frame is 100 MB with a 23 KB pitch).
 inline bool fits_u32(int step, int rows) { return step > 0 && rows > 0 && step < (1 << 24) && rows < (1 << 24) && (uint64_t)step * (uint64_t)rows < (1ull << 32); }
 
-inline uint32_t pack_bg(const uint8_t bg[3]) { return (uint32_t)bg[0] | ((uint32_t)bg[1] << 8) | ((uint32_t)bg[2] << 16); }
-
-// cv::getPerspectiveTransform (OpenCV 4.8 imgproc; call site Math/WarpMesh.cpp:214): 8x8 double system,
-// LU with partial pivoting.  Maps src[i] -> dst[i].
-bool perspective_transform(const float src[8], const float dst[8], double M[9])
+// a plane of rows x cols pixels of `bpp` bytes, `step` bytes apart, as every kernel needs it: there, not empty, rows inside the pitch, addressable
+inline bool remap_plane_ok(const void* p, int step, int rows, int cols, int bpp)
 {
-    double A[8][8], B[8];
-    for (int i = 0; i < 4; i++)
-    {
-        const double x = src[2 * i], y = src[2 * i + 1], u = dst[2 * i], v = dst[2 * i + 1];
-        A[i][0] = A[i + 4][3] = x;  A[i][1] = A[i + 4][4] = y;  A[i][2] = A[i + 4][5] = 1.0;
-        A[i][3] = A[i][4] = A[i][5] = A[i + 4][0] = A[i + 4][1] = A[i + 4][2] = 0.0;
-        A[i][6] = -x * u;  A[i][7] = -y * u;  A[i + 4][6] = -x * v;  A[i + 4][7] = -y * v;
-        B[i] = u;  B[i + 4] = v;
-    }
-    for (int i = 0; i < 8; i++)
-    {
-        int piv = i;
-        for (int j = i + 1; j < 8; j++) if (std::fabs(A[j][i]) > std::fabs(A[piv][i])) piv = j;
-        if (std::fabs(A[piv][i]) < 2.220446049250313e-16 * 100) return false;
-        if (piv != i) { for (int j = i; j < 8; j++) std::swap(A[i][j], A[piv][j]); std::swap(B[i], B[piv]); }
-        const double d = -1.0 / A[i][i];
-        for (int j = i + 1; j < 8; j++)
-        {
-            const double alpha = A[j][i] * d;
-            for (int q = i + 1; q < 8; q++) A[j][q] += alpha * A[i][q];
-            B[j] += alpha * B[i];
-        }
-    }
-    for (int i = 7; i >= 0; i--)
-    {
-        double s = B[i];
-        for (int q = i + 1; q < 8; q++) s -= A[i][q] * B[q];
-        B[i] = s / A[i][i];
-    }
-    for (int q = 0; q < 8; q++) M[q] = B[q];
-    M[8] = 1.0;
-    return true;
+    return p != nullptr && cols > 0 && rows > 0 && step >= bpp * cols && fits_u32(step, rows);
 }
 
+inline bool remap_mesh_ok(const float* mesh, int mesh_rows, int mesh_cols) { return mesh != nullptr && mesh_rows >= 2 && mesh_cols >= 2; }   // WarpMesh::MinimumSize
+
+inline uint32_t pack_bg(const uint8_t bg[3]) { return (uint32_t)bg[0] | ((uint32_t)bg[1] << 8) | ((uint32_t)bg[2] << 16); }
+
+// ---- a mesh larger than 2 x 2 on its way to one launch ---------------------------------------------------------------------------------------------
+// What a mesh kernel takes: the staged vertices and the two INTER_LINEAR tables of the frame size.
+struct StagedMesh { const float* d_mesh; int mesh_cols, mesh_floats; const LinTabEntry* xtab; const LinTabEntry* ytab; };
+
+// The staging protocol, owned here: the tables first -- once the mesh is staged nothing may fail before lvk_stage_consumed (a slot whose event was never
+// re-recorded could be rewritten while its copy is still in flight) --, then the mesh into a slot of the context's ring, launch(staged) (which cannot
+// return early: it returns nothing), and the slot given up behind it, also after a failed launch.  A launch error is reported in preference to the
+// result of giving the slot up.
+template <class Launch>
+inline int with_staged_mesh(lvk_hip_ctx* ctx, hipStream_t stream, const float* mesh, int mesh_rows, int mesh_cols, int rows, int cols, const Launch& launch)
+{
+    const size_t mesh_bytes = (size_t)mesh_rows * mesh_cols * 2 * sizeof(float);
+    LVK_HIP_REQUIRE(ctx, mesh_bytes <= lvk_hip_ctx::kStageBytes);
+    StagedMesh m{nullptr, mesh_cols, mesh_rows * mesh_cols * 2, nullptr, nullptr};
+    int rc;
+    if ((rc = lvk_get_lintab(ctx, mesh_cols, cols, false, &m.xtab)) != LVK_HIP_OK) return rc;
+    if ((rc = lvk_get_lintab(ctx, mesh_rows, rows, true, &m.ytab)) != LVK_HIP_OK) return rc;
+    void* d_mesh = nullptr; int stage_slot = 0;
+    if ((rc = lvk_stage_params(ctx, stream, mesh, mesh_bytes, &d_mesh, &stage_slot)) != LVK_HIP_OK) return rc;
+    m.d_mesh = (const float*)d_mesh;
+    static_assert(std::is_void_v<decltype(launch(m))>, "the launch cannot report a failure of its own: nothing returns between staging and lvk_stage_consumed");
+    launch(m);
+    const hipError_t le = hipGetLastError();
+    rc = lvk_stage_consumed(ctx, stage_slot, stream);               // the slot is free again once this kernel has read the mesh
+    if (le != hipSuccess) return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(le));
+    return rc;
+}
 
 } // namespace

@@ -106,17 +106,9 @@ template <class Coord>
 __device__ __forceinline__ void remap_strip_gray(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
                                                  uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols, const Coord& coord, uint32_t bg)
 {
-    const int strips_x = (gray_span(dst_cols) + STRIP_W - 1) / STRIP_W, strips_y = (dst_rows + STRIP_H - 1) / STRIP_H;
-    const int nstrips = strips_x * strips_y;
-    const int band = (nstrips + NUM_XCD - 1) / NUM_XCD;
-    const int xcd = (int)(blockIdx.x % NUM_XCD);
-    const int kstride = (int)(gridDim.x / NUM_XCD);
-    for (int k = (int)(blockIdx.x / NUM_XCD); k < band; k += kstride)
-    {
-        const int strip = xcd * band + k;
-        if (strip >= nstrips) break;                                    // block-uniform
+    walk_strips(dst_rows, gray_span(dst_cols), [&](int strip, int /*nstrips*/, int strips_x, int /*parity*/) __attribute__((always_inline)) {
         remap_one_strip_gray(src, src_step, src_rows, src_cols, dst, dst_step, dst_rows, dst_cols, coord, bg, strip, strips_x);
-    }
+    });
 }
 
 // CO: the same body under a name of its own for the persistent grid of the overlap mode (profiles tell the two apart).  remap.hip marks its `_co` kernels
@@ -128,9 +120,9 @@ void k_remap_homography_gray(const uint8_t* __restrict__ src, int src_step, int 
                              uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols,
                              int off_x, int off_y, HomographyArgs H, LensArgs L, uint32_t bg)
 {
-    const HomographyCoord hc{H, off_x, off_y};
-    if constexpr (LENS) remap_strip_gray(src, src_step, src_rows, src_cols, dst, dst_step, dst_rows, dst_cols, LensCoord<HomographyCoord>{hc, L, src_rows, src_cols}, bg);
-    else remap_strip_gray(src, src_step, src_rows, src_cols, dst, dst_step, dst_rows, dst_cols, hc, bg);
+    with_homography_coord<LENS>(H, off_x, off_y, L, src_rows, src_cols, [&](const auto& coord) __attribute__((always_inline)) {
+        remap_strip_gray(src, src_step, src_rows, src_cols, dst, dst_step, dst_rows, dst_cols, coord, bg);
+    });
 }
 
 template <bool LENS, bool CO>
@@ -139,18 +131,7 @@ void k_remap_mesh_gray(const uint8_t* __restrict__ src, int src_step, int rows, 
                        const float* __restrict__ mesh, int mesh_cols, int mesh_floats,
                        const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, LensArgs L, uint32_t bg)
 {
-    if (mesh_to_lds(mesh, mesh_floats))
-    {
-        const MeshCoordT<true> mc{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows};
-        if constexpr (LENS) remap_strip_gray(src, src_step, rows, cols, dst, dst_step, rows, cols, LensCoord<MeshCoordT<true>>{mc, L, rows, cols}, bg);
-        else remap_strip_gray(src, src_step, rows, cols, dst, dst_step, rows, cols, mc, bg);
-    }
-    else
-    {
-        const MeshCoordT<false> mc{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows};
-        if constexpr (LENS) remap_strip_gray(src, src_step, rows, cols, dst, dst_step, rows, cols, LensCoord<MeshCoordT<false>>{mc, L, rows, cols}, bg);
-        else remap_strip_gray(src, src_step, rows, cols, dst, dst_step, rows, cols, mc, bg);
-    }
+    LVK_WITH_MESH_COORD(LENS, L, rows, cols, remap_strip_gray(src, src_step, rows, cols, dst, dst_step, rows, cols, coord, bg))
 }
 
 __global__ __launch_bounds__(256) LVK_REMAP_ATTR
@@ -160,110 +141,67 @@ void k_remap_map_gray(const uint8_t* __restrict__ src, int src_step, int rows, i
     remap_strip_gray(src, src_step, rows, cols, dst, dst_step, rows, cols, MapCoord{map, map_step}, bg);
 }
 
-// source and destination of a remap must not share a byte: the kernel reads a neighbourhood of what another thread writes
-bool gray_disjoint(const void* a, int a_step, int a_rows, int a_cols, const void* b, int b_step, int b_rows, int b_cols)
+// The forms of a one-channel family as launch_remap() takes them, [persistent grid][1-LSB][lens]: no twin, so both precisions are the one kernel (and a
+// precision that is neither, which the one-channel launchers do not check, runs it too).  Here and not in remap_core.hpp: these kernels are plain
+// templates on <LENS, CO>, not products of LVK_REMAP_KERNEL
+#define LVK_GRAY_FORMS(K) RemapForms<decltype(&K<false, false>)>{ { { { K<false, false>, K<true, false> }, { K<false, false>, K<true, false> } }, \
+                                                                    { { K<false, true>, K<true, true> }, { K<false, true>, K<true, true> } } } }
+
+// the planes of a one-channel remap: both well-formed, and no byte shared -- the kernel reads a neighbourhood of what another thread writes
+bool gray_planes_ok(const void* src, int src_step, int src_rows, int src_cols, const void* dst, int dst_step, int dst_rows, int dst_cols)
 {
-    return !lvk_pitched_overlap(a, a_step, a_rows, a_cols, b, b_step, b_rows, b_cols);
+    return remap_plane_ok(src, src_step, src_rows, src_cols, 1) && remap_plane_ok(dst, dst_step, dst_rows, dst_cols, 1) &&
+           !lvk_pitched_overlap(src, src_step, src_rows, src_cols, dst, dst_step, dst_rows, dst_cols);
 }
 
 } // namespace
 
-int lvk_launch_remap_homography_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int src_rows, int src_cols,
-                                     void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y,
-                                     const float H[9], uint8_t bg, const LensArgs* lens, bool co)
+int lvk_launch_remap_homography_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
+                                     void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], uint8_t bg, const RemapLaunch& o)
 {
-    LVK_HIP_REQUIRE(ctx, d_src != nullptr && d_dst != nullptr && H != nullptr);
-    LVK_HIP_REQUIRE(ctx, src_cols > 0 && src_rows > 0 && dst_cols > 0 && dst_rows > 0);
-    LVK_HIP_REQUIRE(ctx, src_step >= src_cols && dst_step >= dst_cols);
-    LVK_HIP_REQUIRE(ctx, fits_u32(src_step, src_rows) && fits_u32(dst_step, dst_rows));
-    LVK_HIP_REQUIRE(ctx, gray_disjoint(d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols));
+    LVK_HIP_REQUIRE(ctx, H != nullptr && gray_planes_ok(d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols));
     HomographyArgs args;
     std::memcpy(args.h, H, sizeof(args.h));
-    const LensArgs no_lens{};
-    const LensArgs& L = lens ? *lens : no_lens;
-    const dim3 block(256), grid = co ? lvk_co_grid(ctx, dst_rows, gray_span(dst_cols)) : remap_grid(dst_rows, gray_span(dst_cols));
-#define LVK_LAUNCH_GRAY_H(LENS, CO) hipLaunchKernelGGL((k_remap_homography_gray<LENS, CO>), grid, block, 0, stream, (const uint8_t*)d_src, src_step, src_rows, src_cols, \
-                                                       (uint8_t*)d_dst, dst_step, dst_rows, dst_cols, off_x, off_y, args, L, (uint32_t)bg)
-    if (lens) { if (co) LVK_LAUNCH_GRAY_H(true, true); else LVK_LAUNCH_GRAY_H(true, false); }
-    else { if (co) LVK_LAUNCH_GRAY_H(false, true); else LVK_LAUNCH_GRAY_H(false, false); }
-#undef LVK_LAUNCH_GRAY_H
+    launch_remap(ctx, LVK_GRAY_FORMS(k_remap_homography_gray), o.lens != nullptr, dst_rows, gray_span(dst_cols), o, 0, (const uint8_t*)d_src, src_step, src_rows, src_cols,
+                 (uint8_t*)d_dst, dst_step, dst_rows, dst_cols, off_x, off_y, args, o.lens ? *o.lens : LensArgs{}, (uint32_t)bg);
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
 }
 
-int lvk_launch_remap_mesh_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
-                               const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const LensArgs* lens, bool co)
+int lvk_launch_remap_mesh_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                               const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const RemapLaunch& o)
 {
-    LVK_HIP_REQUIRE(ctx, d_src != nullptr && d_dst != nullptr && mesh != nullptr);
-    LVK_HIP_REQUIRE(ctx, cols > 0 && rows > 0);
-    LVK_HIP_REQUIRE(ctx, mesh_rows >= 2 && mesh_cols >= 2);           // WarpMesh::MinimumSize
-    LVK_HIP_REQUIRE(ctx, src_step >= cols && dst_step >= cols);
-    LVK_HIP_REQUIRE(ctx, fits_u32(src_step, rows) && fits_u32(dst_step, rows));
-    LVK_HIP_REQUIRE(ctx, gray_disjoint(d_src, src_step, rows, cols, d_dst, dst_step, rows, cols));
-    const size_t mesh_bytes = (size_t)mesh_rows * mesh_cols * 2 * sizeof(float);
-    LVK_HIP_REQUIRE(ctx, mesh_bytes <= lvk_hip_ctx::kStageBytes);
-
-    // the tables first: once the mesh is staged nothing may fail before lvk_stage_consumed (see lvk_launch_remap_mesh)
-    const LinTabEntry *xtab = nullptr, *ytab = nullptr;
-    int rc;
-    if ((rc = lvk_get_lintab(ctx, mesh_cols, cols, false, &xtab)) != LVK_HIP_OK) return rc;
-    if ((rc = lvk_get_lintab(ctx, mesh_rows, rows, true, &ytab)) != LVK_HIP_OK) return rc;
-    void* d_mesh = nullptr; int stage_slot = 0;
-    if ((rc = lvk_stage_params(ctx, stream, mesh, mesh_bytes, &d_mesh, &stage_slot)) != LVK_HIP_OK) return rc;
-
-    const LensArgs no_lens{};
-    const LensArgs& L = lens ? *lens : no_lens;
-    const dim3 block(256), grid = co ? lvk_co_grid(ctx, rows, gray_span(cols)) : remap_grid(rows, gray_span(cols));
-#define LVK_LAUNCH_GRAY_M(LENS, CO) hipLaunchKernelGGL((k_remap_mesh_gray<LENS, CO>), grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step, \
-                                                       (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, L, (uint32_t)bg)
-    if (lens) { if (co) LVK_LAUNCH_GRAY_M(true, true); else LVK_LAUNCH_GRAY_M(true, false); }
-    else { if (co) LVK_LAUNCH_GRAY_M(false, true); else LVK_LAUNCH_GRAY_M(false, false); }
-#undef LVK_LAUNCH_GRAY_M
-    const hipError_t le = hipGetLastError();
-    rc = lvk_stage_consumed(ctx, stage_slot, stream);               // the slot is free again once this kernel has read the mesh (also after a failed launch)
-    if (le != hipSuccess) return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(le));
-    return rc;
+    LVK_HIP_REQUIRE(ctx, remap_mesh_ok(mesh, mesh_rows, mesh_cols) && gray_planes_ok(d_src, src_step, rows, cols, d_dst, dst_step, rows, cols));
+    return with_staged_mesh(ctx, o.stream, mesh, mesh_rows, mesh_cols, rows, cols, [&](const StagedMesh& m) {
+        launch_remap(ctx, LVK_GRAY_FORMS(k_remap_mesh_gray), o.lens != nullptr, rows, gray_span(cols), o, 0, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step,
+                     m.d_mesh, m.mesh_cols, m.mesh_floats, m.xtab, m.ytab, o.lens ? *o.lens : LensArgs{}, (uint32_t)bg);
+    });
 }
 
-int lvk_launch_remap_map_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
-                              void* d_dst, int dst_step, const void* d_map, int map_step, uint8_t bg)
+int lvk_launch_remap_map_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
+                              void* d_dst, int dst_step, const void* d_map, int map_step, uint8_t bg, const RemapLaunch& o)
 {
-    LVK_HIP_REQUIRE(ctx, d_src != nullptr && d_dst != nullptr && d_map != nullptr);
-    LVK_HIP_REQUIRE(ctx, cols > 0 && rows > 0 && src_step >= cols && dst_step >= cols && map_step >= 8 * cols);
+    LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_map, map_step, rows, cols, 8) && gray_planes_ok(d_src, src_step, rows, cols, d_dst, dst_step, rows, cols));
     LVK_HIP_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_map) | (uintptr_t)map_step) & 7u) == 0);
-    LVK_HIP_REQUIRE(ctx, fits_u32(src_step, rows) && fits_u32(dst_step, rows) && fits_u32(map_step, rows));
-    LVK_HIP_REQUIRE(ctx, gray_disjoint(d_src, src_step, rows, cols, d_dst, dst_step, rows, cols));
-    hipLaunchKernelGGL(k_remap_map_gray, remap_grid(rows, gray_span(cols)), dim3(256), 0, stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step,
+    // (one kernel, no family to pick from: launched directly on the full grid; of `o` only the stream is read)
+    hipLaunchKernelGGL(k_remap_map_gray, remap_grid(rows, gray_span(cols)), dim3(256), 0, o.stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step,
                        (const uint8_t*)d_map, map_step, (uint32_t)bg);
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
 }
 
-// WarpMesh::apply on a one-channel frame: a 2 x 2 mesh goes through cv::getPerspectiveTransform + the homography kernel (WarpMesh.cpp:194-217, as in
-// lvk_launch_warpmesh_apply_lens), anything larger through the mesh kernel
-int lvk_launch_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
-                                        const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const LensArgs* lens, bool co)
+// WarpMesh::apply on a one-channel frame: a 2 x 2 mesh goes through the homography kernel, anything larger through the mesh kernel
+int lvk_launch_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                                        const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const RemapLaunch& o)
 {
-    LVK_HIP_REQUIRE(ctx, mesh != nullptr && mesh_rows >= 2 && mesh_cols >= 2);
+    LVK_HIP_REQUIRE(ctx, remap_mesh_ok(mesh, mesh_rows, mesh_cols));
     if (mesh_rows == 2 && mesh_cols == 2)
     {
-        const float w = (float)cols, h = (float)rows;
-        const float dstp[8] = { 0, 0, w, 0, 0, h, w, h };
-        float srcp[8];
-        for (int i = 0; i < 4; i++)
-        {
-            // Point2f * Scalar: float * double, rounded back to float (Functions/Extensions.cpp operator*(Point2f, Scalar))
-            srcp[2 * i] = dstp[2 * i] + (float)((double)mesh[2 * i] * (double)cols);
-            srcp[2 * i + 1] = dstp[2 * i + 1] + (float)((double)mesh[2 * i + 1] * (double)rows);
-        }
-        double M[9];
-        if (!perspective_transform(dstp, srcp, M))
-            for (int q = 0; q < 9; q++) M[q] = (q % 4 == 0) ? 1.0 : 0.0;
         float H[9];
-        for (int q = 0; q < 9; q++) H[q] = (float)M[q];              // Image.cpp:137-139
-        return lvk_launch_remap_homography_gray(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, rows, cols, 0, 0, H, bg, lens, co);
+        lvkh::mesh2x2_to_homography(mesh, rows, cols, H);
+        return lvk_launch_remap_homography_gray(ctx, d_src, src_step, rows, cols, d_dst, dst_step, rows, cols, 0, 0, H, bg, o);
     }
-    return lvk_launch_remap_mesh_gray(ctx, stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, lens, co);
+    return lvk_launch_remap_mesh_gray(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, o);
 }
 
 extern "C" {
@@ -272,28 +210,28 @@ int lvk_hip_remap_homography_gray(lvk_hip_ctx* ctx, const void* d_src, int src_s
                                   void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], uint8_t bg)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_remap_homography_gray(ctx, ctx->stream, d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols, off_x, off_y, H, bg, nullptr, false);
+    return lvk_launch_remap_homography_gray(ctx, d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols, off_x, off_y, H, bg, RemapLaunch{ctx->stream});
 }
 
 int lvk_hip_remap_mesh_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step,
                             const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_remap_mesh_gray(ctx, ctx->stream, d_src, src_step, src_rows, src_cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, nullptr, false);
+    return lvk_launch_remap_mesh_gray(ctx, d_src, src_step, src_rows, src_cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, RemapLaunch{ctx->stream});
 }
 
 int lvk_hip_remap_map_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
                            const void* d_map, int map_step, uint8_t bg)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_remap_map_gray(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, d_map, map_step, bg);
+    return lvk_launch_remap_map_gray(ctx, d_src, src_step, rows, cols, d_dst, dst_step, d_map, map_step, bg, RemapLaunch{ctx->stream});
 }
 
 int lvk_hip_warpmesh_apply_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
                                 const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg)
 {
     LVK_HIP_ENTRY(ctx);
-    return lvk_launch_warpmesh_apply_lens_gray(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, nullptr, false);
+    return lvk_launch_warpmesh_apply_lens_gray(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, RemapLaunch{ctx->stream});
 }
 
 int lvk_hip_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
@@ -305,7 +243,7 @@ int lvk_hip_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, const void* d_src, int sr
     const int rc = lvk_lens_model_build(*lens, rows, cols, m);
     if (rc != LVK_HIP_OK) return ctx->fail(rc, "invalid camera profile");
     std::memcpy(a.f, m.f, sizeof(a.f));
-    return lvk_launch_warpmesh_apply_lens_gray(ctx, ctx->stream, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, &a, false);
+    return lvk_launch_warpmesh_apply_lens_gray(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, RemapLaunch{ctx->stream, LVK_REMAP_EXACT, &a});
 }
 
 } // extern "C"

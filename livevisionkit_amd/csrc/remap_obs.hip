@@ -83,25 +83,25 @@ struct Sink444
     }
 };
 
-// (each LVK_REMAP_KERNEL below defines the exact kernel NAME and its 1-LSB twin NAME_r1 from one body -- remap_core.hpp)
+// (each LVK_REMAP_KERNEL below defines the exact kernel NAME and its 1-LSB twin NAME_r1 from one body; remap_homography and LVK_WITH_MESH_COORD are the bodies of
+//  the kernels with and without the lens pre-warp -- remap_core.hpp)
 LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_homography_planes,
                  (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink, HomographyArgs H, uint32_t bg),
 {
-    remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, HomographyCoord{H, 0, 0}, bg);
+    remap_homography<true, W, false>(src, src_step, rows, cols, sink, rows, cols, 0, 0, H, LensArgs{}, bg);
 })
 
 LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_homography_lens_planes,
                  (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink, HomographyArgs H, LensArgs L, uint32_t bg),
 {
-    remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<HomographyCoord>{HomographyCoord{H, 0, 0}, L, rows, cols}, bg);
+    remap_homography<true, W, true>(src, src_step, rows, cols, sink, rows, cols, 0, 0, H, L, bg);
 })
 
 LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_mesh_planes,
                  (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink,
                   const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab, uint32_t bg),
 {
-    if (mesh_to_lds(mesh, mesh_floats)) remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
-    else remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, bg);
+    LVK_WITH_MESH_COORD(false, LensArgs{}, rows, cols, (remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, coord, bg)))
 })
 
 LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_mesh_lens_planes,
@@ -109,60 +109,29 @@ LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_mesh_lens_planes,
                   const float* __restrict__ mesh, int mesh_cols, int mesh_floats, const LinTabEntry* __restrict__ xtab, const LinTabEntry* __restrict__ ytab,
                   LensArgs L, uint32_t bg),
 {
-    if (mesh_to_lds(mesh, mesh_floats))
-        remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<true>>{MeshCoordT<true>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
-    else
-        remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, LensCoord<MeshCoordT<false>>{MeshCoordT<false>{mesh, mesh_cols, xtab, ytab, (float)cols, (float)rows}, L, rows, cols}, bg);
+    LVK_WITH_MESH_COORD(true, L, rows, cols, (remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, coord, bg)))
 })
 
+// (the family's "flag" is the sink type: one form per precision)
 template <class Sink>
-int launch_planes(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols, const Sink& sink,
-                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const LensArgs* lens, bool co, int precision)
+int launch_planes(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, const Sink& sink,
+                  const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const RemapLaunch& o)
 {
-    const dim3 block(256), grid = co ? lvk_co_grid(ctx, rows, cols) : remap_grid(rows, cols);
-    int stage_slot = -1;
-    // one launch: the exact kernel or its 1-LSB twin
-#define LVK_LAUNCH_PLANES(K, ...)                                                                                                                              \
-    do {                                                                                                                                                       \
-        if (precision == LVK_REMAP_1LSB) hipLaunchKernelGGL(K##_r1<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, __VA_ARGS__, pack_bg(bg)); \
-        else hipLaunchKernelGGL(K<Sink>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, sink, __VA_ARGS__, pack_bg(bg));                  \
-    } while (0)
     if (mesh_rows == 2 && mesh_cols == 2)
     {
-        const float w = (float)cols, h = (float)rows;                 // WarpMesh.cpp:194-217, as in lvk_launch_warpmesh_apply_lens
-        const float dstp[8] = { 0, 0, w, 0, 0, h, w, h };
-        float srcp[8];
-        for (int i = 0; i < 4; i++)
-        {
-            srcp[2 * i] = dstp[2 * i] + (float)((double)mesh[2 * i] * (double)cols);
-            srcp[2 * i + 1] = dstp[2 * i + 1] + (float)((double)mesh[2 * i + 1] * (double)rows);
-        }
-        double M[9];
-        if (!perspective_transform(dstp, srcp, M))
-            for (int q = 0; q < 9; q++) M[q] = (q % 4 == 0) ? 1.0 : 0.0;
-        HomographyArgs args;
-        for (int q = 0; q < 9; q++) args.h[q] = (float)M[q];
-        if (lens) LVK_LAUNCH_PLANES(k_remap_homography_lens_planes, args, *lens);
-        else LVK_LAUNCH_PLANES(k_remap_homography_planes, args);
+        HomographyArgs H;
+        lvkh::mesh2x2_to_homography(mesh, rows, cols, H.h);
+        if (o.lens) launch_remap(ctx, LVK_REMAP_FORMS(k_remap_homography_lens_planes, Sink, Sink), false, rows, cols, o, 0, (const uint8_t*)d_src, src_step, rows, cols, sink, H, *o.lens, pack_bg(bg));
+        else launch_remap(ctx, LVK_REMAP_FORMS(k_remap_homography_planes, Sink, Sink), false, rows, cols, o, 0, (const uint8_t*)d_src, src_step, rows, cols, sink, H, pack_bg(bg));
+        LVK_HIP_CHECK(ctx, hipGetLastError());
+        return LVK_HIP_OK;
     }
-    else
-    {
-        const size_t mesh_bytes = (size_t)mesh_rows * mesh_cols * 2 * sizeof(float);
-        LVK_HIP_REQUIRE(ctx, mesh_bytes <= lvk_hip_ctx::kStageBytes);
-        const LinTabEntry *xtab = nullptr, *ytab = nullptr;          // before the mesh is staged (see lvk_launch_remap_mesh)
-        int rc;
-        if ((rc = lvk_get_lintab(ctx, mesh_cols, cols, false, &xtab)) != LVK_HIP_OK) return rc;
-        if ((rc = lvk_get_lintab(ctx, mesh_rows, rows, true, &ytab)) != LVK_HIP_OK) return rc;
-        void* d_mesh = nullptr;
-        if ((rc = lvk_stage_params(ctx, stream, mesh, mesh_bytes, &d_mesh, &stage_slot)) != LVK_HIP_OK) return rc;
-        if (lens) LVK_LAUNCH_PLANES(k_remap_mesh_lens_planes, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab, *lens);
-        else LVK_LAUNCH_PLANES(k_remap_mesh_planes, (const float*)d_mesh, mesh_cols, mesh_rows * mesh_cols * 2, xtab, ytab);
-    }
-#undef LVK_LAUNCH_PLANES
-    const hipError_t le = hipGetLastError();
-    const int src = stage_slot >= 0 ? lvk_stage_consumed(ctx, stage_slot, stream) : LVK_HIP_OK;
-    if (le != hipSuccess) return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(le));
-    return src;
+    return with_staged_mesh(ctx, o.stream, mesh, mesh_rows, mesh_cols, rows, cols, [&](const StagedMesh& m) {
+        if (o.lens) launch_remap(ctx, LVK_REMAP_FORMS(k_remap_mesh_lens_planes, Sink, Sink), false, rows, cols, o, 0, (const uint8_t*)d_src, src_step, rows, cols, sink,
+                                 m.d_mesh, m.mesh_cols, m.mesh_floats, m.xtab, m.ytab, *o.lens, pack_bg(bg));
+        else launch_remap(ctx, LVK_REMAP_FORMS(k_remap_mesh_planes, Sink, Sink), false, rows, cols, o, 0, (const uint8_t*)d_src, src_step, rows, cols, sink,
+                          m.d_mesh, m.mesh_cols, m.mesh_floats, m.xtab, m.ytab, pack_bg(bg));
+    });
 }
 
 } // namespace
@@ -178,36 +147,34 @@ bool lvk_remap_obs_fusable(int video_format)
 }
 
 // WarpMesh::apply + FrameIngest::to_obs of `video_format` in one kernel; the planes' geometry has been checked by the caller (lvk_stab_push_planes).
-int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, hipStream_t stream, int video_format, const void* d_src, int src_step, int rows, int cols,
-                                  void* const planes[3], const int steps[3], const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3],
-                                  const LensArgs* lens, bool co, int precision)
+int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, int video_format, const void* d_src, int src_step, int rows, int cols,
+                                  void* const planes[3], const int steps[3], const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const RemapLaunch& o)
 {
-    LVK_HIP_REQUIRE(ctx, remap_precision_known(precision));
-    LVK_HIP_REQUIRE(ctx, d_src && planes && steps && planes[0] && mesh && bg && mesh_rows >= 2 && mesh_cols >= 2 && rows > 0 && cols > 0 && src_step >= 3 * cols);
-    LVK_HIP_REQUIRE(ctx, fits_u32(src_step, rows) && fits_u32(steps[0], rows));
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(o.precision));
+    LVK_HIP_REQUIRE(ctx, planes && steps && bg && remap_mesh_ok(mesh, mesh_rows, mesh_cols) && remap_plane_ok(d_src, src_step, rows, cols, 3));
     uint8_t* p0 = (uint8_t*)planes[0]; uint8_t* p1 = (uint8_t*)planes[1]; uint8_t* p2 = (uint8_t*)planes[2];
-    const bool planar = video_format == LVK_VIDEO_FORMAT_I422 || video_format == LVK_VIDEO_FORMAT_I42A || video_format == LVK_VIDEO_FORMAT_I444 || video_format == LVK_VIDEO_FORMAT_YUVA;
-    if (planar) LVK_HIP_REQUIRE(ctx, p1 && p2 && fits_u32(steps[1], rows) && fits_u32(steps[2], rows));
+    // plane i holds rows x `c` samples of `bpp` bytes
+    auto plane_ok = [&](int i, int c, int bpp) { return remap_plane_ok(planes[i], steps[i], rows, c, bpp); };
     switch (video_format)
     {
     case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= cols && steps[1] >= cols / 2 && steps[2] >= cols / 2);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 1) && plane_ok(1, cols / 2, 1) && plane_ok(2, cols / 2, 1));
+        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, o);
     case LVK_VIDEO_FORMAT_YUY2:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
+        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
     case LVK_VIDEO_FORMAT_YVYU:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<2>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
+        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<2>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
     case LVK_VIDEO_FORMAT_UYVY:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && steps[0] >= 2 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink422<3>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
+        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<3>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
     case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA:
-        LVK_HIP_REQUIRE(ctx, steps[0] >= cols && steps[1] >= cols && steps[2] >= cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink444<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
+        LVK_HIP_REQUIRE(ctx, plane_ok(0, cols, 1) && plane_ok(1, cols, 1) && plane_ok(2, cols, 1));
+        return launch_planes(ctx, d_src, src_step, rows, cols, Sink444<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, o);
     case LVK_VIDEO_FORMAT_AYUV:
-        LVK_HIP_REQUIRE(ctx, steps[0] >= 4 * cols);
-        return launch_planes(ctx, stream, d_src, src_step, rows, cols, Sink444<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, lens, co, precision);
+        LVK_HIP_REQUIRE(ctx, plane_ok(0, cols, 4));
+        return launch_planes(ctx, d_src, src_step, rows, cols, Sink444<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
     }
     return ctx->fail(LVK_HIP_ERR_ARG, "lvk_launch_warpmesh_apply_obs: no fused sink for video format " + std::to_string(video_format));
 }

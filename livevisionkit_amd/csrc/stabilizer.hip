@@ -453,7 +453,7 @@ int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows
         // a remap whose stores cross the host link (lvk_hip_stab_push_yuv420_host) is bound by the link, not by the chip: ONE block per CU
         // for a free-running caller -- measured (two upload streams at the time) 2 800 frames/s against 2 560 with the 4 blocks per CU of a device-resident stream (the
         // stores of more blocks only fill the link's write queue sooner, which stalls the tracker's kernels), 2 450 with one per two CUs
-        ctx->co_blocks_per_cu = (persistent && st->host_direct_now) ? 1 : 0;
+        const int co_blocks_per_cu = (persistent && st->host_direct_now) ? 1 : 0;
         if (side && (rc = st->bulk_stream_sees_caller_work()) != LVK_HIP_OK) return rc;
         if (st->remap_wait) { const hipEvent_t e = st->remap_wait; st->remap_wait = nullptr; LVK_HIP_CHECK(ctx, hipStreamWaitEvent(rs, e, 0)); }
         st->trace.mark(HostTrace::EMIT_WAITS);
@@ -470,21 +470,21 @@ int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows
                 std::memcpy(lens_other.f, m.f, sizeof(lens_other.f)); lens_args = &lens_other;
             }
         }
+        const RemapLaunch how{rs, st->remap_precision, lens_args, persistent, co_blocks_per_cu};
         if (mesh && o420 && o420->y && o420->vf != 0)
         {
-            rc = lvk_launch_warpmesh_apply_obs(ctx, rs, o420->vf, f.d_ptr, f.step, f.rows, f.cols, o420->p, o420->s, mesh->off.data(), mesh->rows, mesh->cols, bg, lens_args, persistent, st->remap_precision);
+            rc = lvk_launch_warpmesh_apply_obs(ctx, o420->vf, f.d_ptr, f.step, f.rows, f.cols, o420->p, o420->s, mesh->off.data(), mesh->rows, mesh->cols, bg, how);
             o420->used = true;
         }
         else if (mesh && o420 && o420->y)
         {
-            rc = lvk_launch_warpmesh_apply_420(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, o420->y, o420->y_step, o420->u, o420->u_step, o420->v, o420->v_step,
-                                               o420->nv12, mesh->off.data(), mesh->rows, mesh->cols, bg, lens_args, persistent, st->remap_precision);
+            rc = lvk_launch_warpmesh_apply_420(ctx, f.d_ptr, f.step, f.rows, f.cols, o420->y, o420->y_step, o420->u, o420->u_step, o420->v, o420->v_step,
+                                               o420->nv12, mesh->off.data(), mesh->rows, mesh->cols, bg, how);
             o420->used = true;
         }
-        else if (mesh && gray_entry) rc = lvk_launch_warpmesh_apply_lens_gray(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg[0],
-                                                                              lens_args, persistent);
-        else if (mesh) rc = lvk_launch_warpmesh_apply_lens(ctx, rs, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg,
-                                                      f.format == LVK_FORMAT_YUV ? 1 : 0, lens_args, persistent, st->remap_precision);
+        else if (mesh && gray_entry) rc = lvk_launch_warpmesh_apply_lens_gray(ctx, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg[0], how);
+        else if (mesh) rc = lvk_launch_warpmesh_apply_lens(ctx, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg,
+                                                      f.format == LVK_FORMAT_YUV ? 1 : 0, how);
         else
         {
             hipError_t e = hipMemcpy2DAsync(d_out, out_step, f.d_ptr, f.step, (size_t)f.cols * bpp, f.rows, hipMemcpyDeviceToDevice, ctx->stream);

@@ -249,8 +249,37 @@ static void test_truncated_quotient()
     }
 }
 
+// WarpMesh::apply's 2 x 2 route (WarpMesh.cpp:194-217), the one every remap launcher takes: the nine binary32 values of lvkh::mesh2x2_to_homography are
+// the oracle's, bit for bit, over seeded corner offsets within +-0.2 of the frame; a quad whose four source corners coincide has no perspective transform
+// and yields the identity.
+static void test_mesh2x2_to_homography()
+{
+    const int sizes[3][2] = {{2, 2}, {67, 131}, {2160, 3840}};
+    std::mt19937 rng(2024); std::uniform_real_distribution<float> u(-0.2f, 0.2f);
+    for (const auto& sz : sizes)
+        for (int trial = 0; trial < 300; trial++)
+        {
+            float mesh[8], got[9], want[9];
+            for (float& v : mesh) v = u(rng);
+            lvkh::mesh2x2_to_homography(mesh, sz[0], sz[1], got);
+            CHECK(lvko_mesh2x2_to_homography(mesh, sz[0], sz[1], want) == 0);
+            CHECK(std::memcmp(got, want, sizeof got) == 0);
+        }
+    for (const auto& sz : sizes)
+    {
+        // offsets that carry every corner onto the frame's origin: (0, 0), (-1, 0), (0, -1), (-1, -1)
+        const float mesh[8] = {0, 0, -1, 0, 0, -1, -1, -1};
+        const float identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        float got[9], want[9];
+        lvkh::mesh2x2_to_homography(mesh, sz[0], sz[1], got);
+        CHECK(lvko_mesh2x2_to_homography(mesh, sz[0], sz[1], want) != 0);     // the oracle reports the failed solve, and returns the identity as well
+        CHECK(std::memcmp(got, identity, sizeof got) == 0 && std::memcmp(want, identity, sizeof want) == 0);
+    }
+}
+
 int main()
 {
+    test_mesh2x2_to_homography();
     test_truncated_quotient();
     test_mesh_constraints_static_band();
     test_feature_grid();

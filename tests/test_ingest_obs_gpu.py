@@ -200,6 +200,43 @@ def test_push_obs_equals_oracle_ingest_filter_egress(ctx, oracle, fmt, size, pre
     gst.close()
 
 
+# field, 16: 16 x 16 x 2 floats, the mesh in LDS; field, 33: 33 x 33 x 2 = 2178 > 2048, the mesh read from global memory; homography: the 2 x 2 route
+@pytest.mark.parametrize("preset,motion", [("field", 16), ("field", 33), ("homography", 2)])
+@pytest.mark.parametrize("lens", [False, True])       # True: the k_remap_mesh_lens_planes / k_remap_homography_lens_planes kernels, which nothing else launches
+@pytest.mark.parametrize("fmt,size", [("UYVY", (66, 130)), ("I444", (66, 130)), ("I422", (8, 258)), ("AYUV", (8, 258))])
+def test_push_obs_fused_mesh_sinks_small_frames(ctx, oracle, fmt, size, lens, preset, motion):
+    """the mesh kernels' fused 4:2:2 / 4:4:4 sinks with and without the fused lens pre-warp, with the mesh in LDS and in global memory, at frames of more
+    than one block with a ragged last strip (66 x 130) and of one wave-, block- and strip-edge shape (8 x 258: 2 pixels past a strip); compared like the
+    streams above, with the oracle's ingest -> filter (.set_lens) -> egress"""
+    import livevisionkit_amd as lvk
+    from tests import oracle_lib, synth
+    from tests.test_stabilizer_gpu import _to_settings
+    from tests.test_config5_gpu import survey_profile
+    (rows, cols), n = size, 8
+    clip, _ = synth.make_clip(rows, cols, n, seed=47, jitter=1.0)
+    s = oracle_lib.preset(preset, predictive_samples=2, min_scene_quality=0.3, min_tracking_quality=0.2)
+    if preset == "field":
+        s.motion_width = s.motion_height = motion
+    ost = oracle_lib.OracleStabilizer(oracle, s)
+    gst = lvk.StabilizationFilter(_to_settings(s), context=ctx)
+    if lens:
+        ost.set_lens(survey_profile(rows, cols)); gst.set_lens(survey_profile(rows, cols))
+    ffmt = ctx.obs_frame_format(fmt)
+    emitted = 0
+    for i, (planes, packed) in enumerate(_obs_stream(oracle, fmt, clip)):
+        w, wts = ost.push(packed, ts=i, fmt=ffmt)
+        out, ots = gst.apply_obs(fmt, [_gpu(p) for p in planes], timestamp=i)
+        ctx.sync()
+        assert (out is None) == (w is None), (fmt, i)
+        if out is not None:
+            emitted += 1
+            assert ots == wts
+            for g, want in zip(out, oracle.egress_obs(fmt, w)):
+                assert np.array_equal(g.cpu().numpy(), want), (fmt, i)
+    assert emitted == n - 2
+    gst.close()
+
+
 def test_push_obs_420_is_push_yuv420(ctx, oracle):
     """the 4:2:0 formats through lvk_hip_stab_push_obs take lvk_hip_stab_push_yuv420's route: same bytes, fused remap + egress (no ingest / egress stage of their own)"""
     import livevisionkit_amd as lvk
