@@ -38,6 +38,16 @@ public:
     {
         return std::unique_ptr<FrameIngest>(new FrameIngest(LVK_VIDEO_FORMAT_Y800, VideoFrame::GRAY, ctx));
     }
+    // RGBA / BGRA / BGRX as what they are: a four-channel VideoFrame::RGBA or VideoFrame::BGRA frame (8UC4; BGRX is a BGRA frame whose fourth byte is
+    // carried like alpha) made of data[0] at linesize[0], and written back the same way -- which StabilizationFilter::apply, WarpMesh::apply and
+    // lvk::remap take.  A selector of its own: Select() keeps its answer for these formats (DirectIngest's three-byte view, FrameIngest.cpp:743-747).
+    // nullptr for any other format.
+    static std::unique_ptr<FrameIngest> SelectRGBX(int obs_format, const std::shared_ptr<hip::Context>& ctx = nullptr)
+    {
+        if (obs_format == LVK_VIDEO_FORMAT_RGBA) return std::unique_ptr<FrameIngest>(new FrameIngest(obs_format, VideoFrame::RGBA, ctx));
+        if (obs_format == LVK_VIDEO_FORMAT_BGRA || obs_format == LVK_VIDEO_FORMAT_BGRX) return std::unique_ptr<FrameIngest>(new FrameIngest(obs_format, VideoFrame::BGRA, ctx));
+        return nullptr;
+    }
 
     int obs_format() const { return m_OBSFormat; }                         // :128-131
     VideoFrame::Format ocl_format() const { return m_OCLFormat; }          // :121-124
@@ -53,6 +63,21 @@ public:
     {
         LVK_HIP_ASSERT(test_obs_frame(src) && (int)src->format == m_OBSFormat);
         const int rows = (int)src->height, cols = (int)src->width;
+        if (four_channel())
+        {
+            // SelectRGBX: the plane IS the frame -- rows of 4 * cols bytes, linesize[0] apart, straight into the 8UC4 frame
+            const size_t row = (size_t)4 * cols, host_step = src->linesize[0] != 0 ? (size_t)src->linesize[0] : row;
+            LVK_HIP_ASSERT(host_step >= row);
+            hip::ContextLock lock(m_ctx->mutex());
+            dst.create({cols, rows}, CV_8UC4, m_ctx);
+            uint8_t* d = static_cast<uint8_t*>(dst.device_ptr());
+            if (host_step == row && dst.step == row) m_ctx->check(lvk_hip_upload(m_ctx->get(), d, src->data[0], row * rows), "FrameIngest::upload_obs_frame");
+            else for (int r = 0; r < rows; r++) m_ctx->check(lvk_hip_upload(m_ctx->get(), d + (size_t)r * dst.step, src->data[0] + (size_t)r * host_step, row), "FrameIngest::upload_obs_frame");
+            m_ctx->check(lvk_hip_sync(m_ctx->get()), "FrameIngest::upload_obs_frame");
+            dst.timestamp = src->timestamp;
+            dst.format = m_OCLFormat;
+            return;
+        }
         Plane pl[3]; const int n = planes(rows, cols, pl);
         hip::ContextLock lock(m_ctx->mutex());
         size_t off[3], total = 0;
@@ -87,9 +112,21 @@ public:
         LVK_HIP_ASSERT(src.format == m_OCLFormat);
         const int rows = (int)dst->height, cols = (int)dst->width;
         LVK_HIP_ASSERT(rows == src.rows && cols == src.cols);
-        Plane pl[3]; const int n = planes(rows, cols, pl);
+        Plane pl[3]; const int n = four_channel() ? 0 : planes(rows, cols, pl);
         if (src.context() && src.context() != m_ctx) m_ctx->wait_for(*src.context());     // (both contexts' locks: before ours is held)
         hip::ContextLock lock(m_ctx->mutex());
+        if (four_channel())
+        {
+            LVK_HIP_ASSERT(src.channels() == 4);
+            const size_t row = (size_t)4 * cols, host_step = dst->linesize[0] != 0 ? (size_t)dst->linesize[0] : row;
+            LVK_HIP_ASSERT(host_step >= row);
+            const uint8_t* d = static_cast<const uint8_t*>(src.device_ptr());
+            if (host_step == row && src.step == row) m_ctx->check(lvk_hip_download(m_ctx->get(), dst->data[0], d, row * rows), "FrameIngest::download_ocl_frame");
+            else for (int r = 0; r < rows; r++) m_ctx->check(lvk_hip_download(m_ctx->get(), dst->data[0] + (size_t)r * host_step, d + (size_t)r * src.step, row), "FrameIngest::download_ocl_frame");
+            m_ctx->check(lvk_hip_sync(m_ctx->get()), "FrameIngest::download_ocl_frame");
+            dst->timestamp = src.timestamp;
+            return;
+        }
         size_t off[3], total = 0;
         for (int i = 0; i < n; i++)
         {
@@ -126,6 +163,8 @@ private:
 
     FrameIngest(int obs_format, VideoFrame::Format ocl_format, const std::shared_ptr<hip::Context>& ctx)
         : m_OBSFormat(obs_format), m_OCLFormat(ocl_format), m_ctx(ctx ? ctx : hip::shared_context()) {}
+
+    bool four_channel() const { return VideoFrame::channels_of(m_OCLFormat) == 4; }      // made by SelectRGBX
 
     // the planes FrameIngest moves for one frame (the alpha planes of I40A / I42A / YUVA stay where they are)
     int planes(int rows, int cols, Plane pl[3]) const

@@ -696,6 +696,9 @@ public:
         const lvk_stab_settings pod = to_pod(settings);
         if (!m_Stab) m_Ctx->check(lvk_hip_stab_create(m_Ctx->get(), &pod, &m_Stab), "StabilizationFilter::configure");
         else m_Ctx->check(lvk_hip_stab_configure(m_Stab, &pod), "StabilizationFilter::configure");
+        // background_colour[3], read by four-channel (BGRA / RGBA) frames only: lvk_stab_settings carries three values
+        const double alpha = settings.background_colour[3];
+        m_Ctx->check(lvk_hip_stab_set_background_alpha(m_Stab, alpha <= 0.0 ? 0 : alpha >= 255.0 ? 255 : (int)alpha), "StabilizationFilter::configure");
         m_Settings = settings;
         static_cast<PathSmootherSettings&>(m_Settings).motion_resolution = settings.motion_resolution;
         static_cast<FrameTrackerSettings&>(m_Settings).motion_resolution = settings.motion_resolution;
@@ -883,14 +886,17 @@ private:
         VideoFrame result;
         lvk_frame_info due{0, 0, 0}, emitted{0, 0, 0};
         const int will_emit = lvk_hip_stab_next_output(m_Stab, in.rows, in.cols, (int)in.format, &due);
-        // a GRAY frame (8UC1: what FrameIngest makes of Y800) goes through lvk_hip_stab_push_gray; a queue holds one format class (restart() to switch)
-        const bool gray = in.format == VideoFrame::GRAY;
-        LVK_HIP_ASSERT(in.channels() == (gray ? 1 : 3));
-        if (will_emit == 1) result.create({due.cols, due.rows}, due.format == LVK_FORMAT_GRAY ? CV_8UC1 : CV_8UC3, m_OutCtx);
+        // a GRAY frame (8UC1: what FrameIngest makes of Y800) goes through lvk_hip_stab_push_gray, a BGRA / RGBA frame (8UC4: FrameIngest::SelectRGBX)
+        // through lvk_hip_stab_push_c4; a queue holds frames of one pixel size (restart() to switch).  The output is created from the DELAYED frame's format.
+        const bool gray = in.format == VideoFrame::GRAY, c4 = in.format == VideoFrame::BGRA || in.format == VideoFrame::RGBA;
+        LVK_HIP_ASSERT(in.channels() == VideoFrame::channels_of(in.format));
+        if (will_emit == 1) result.create({due.cols, due.rows}, VideoFrame::type_of((VideoFrame::Format)due.format), m_OutCtx);
         int produced = 0; uint64_t ts = 0; const void* released = nullptr;
         m_Held.push_back({in.buffer(), in.context()});     // keep the borrowed device buffer alive while it is queued
         const int rc = gray ? lvk_hip_stab_push_gray(m_Stab, in.device_ptr(), (int)in.step, in.rows, in.cols, in.timestamp,
                                                      result.device_ptr(), (int)result.step, result.rows, &produced, &ts, &released, &emitted)
+                     : c4   ? lvk_hip_stab_push_c4(m_Stab, in.device_ptr(), (int)in.step, in.rows, in.cols, in.timestamp, (int)in.format,
+                                                   result.device_ptr(), (int)result.step, result.rows, &produced, &ts, &released, &emitted)
                             : lvk_hip_stab_push(m_Stab, in.device_ptr(), (int)in.step, in.rows, in.cols, in.timestamp, (int)in.format,
                                          result.device_ptr(), (int)result.step, result.rows, &produced, &ts, &released, &emitted);
         if (rc == LVK_HIP_ERR_ARG) m_Held.pop_back();      // (a refused push has queued nothing; after any other error the frame may be queued: keep it alive)

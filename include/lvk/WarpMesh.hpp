@@ -154,14 +154,18 @@ inline void remap(const VideoFrame& src, VideoFrame& dst, const OffsetMap& offse
     const auto& ctx = src.context();
     if (offset_map.context() && offset_map.context() != ctx) ctx->wait_for(*offset_map.context());
     VideoFrame out;                                        // dst may be the object src refers to
-    LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3);
-    out.create(src.size(), src.type(), ctx);               // 8UC3, or 8UC1 (a GRAY frame: the one-channel kernels, background[0])
-    const uint8_t bg[3] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2]};
+    LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3 || src.channels() == 4);
+    // 8UC3, 8UC1 (a GRAY frame: the one-channel kernels, background[0]) or 8UC4 (a BGRA / RGBA frame: the four-channel kernels, all four background values)
+    out.create(src.size(), src.type(), ctx);
+    const uint8_t bg[4] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2], (uint8_t)background[3]};
     {
         hip::ContextLock lock(ctx->mutex());
         if (src.channels() == 1)
             ctx->check(lvk_hip_remap_map_gray(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
                                               offset_map.device_ptr(), (int)offset_map.step, bg[0]), "remap(offset_map)");
+        else if (src.channels() == 4)
+            ctx->check(lvk_hip_remap_map_c4(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
+                                            offset_map.device_ptr(), (int)offset_map.step, bg), "remap(offset_map)");
         else
         ctx->check(lvk_hip_remap_map(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
                                      offset_map.device_ptr(), (int)offset_map.step, bg, src.format == VideoFrame::YUV ? 1 : 0), "remap(offset_map)");
@@ -180,14 +184,17 @@ inline void remap(const VideoFrame& src, VideoFrame& dst, const Homography& homo
     for (int i = 0; i < 9; i++) H[i] = (float)t.data()[i];
     const auto& ctx = src.context();
     VideoFrame out;
-    LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3);
-    out.create(src.size(), src.type(), ctx);               // 8UC3, or 8UC1 (a GRAY frame)
-    const uint8_t bg[3] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2]};
+    LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3 || src.channels() == 4);
+    out.create(src.size(), src.type(), ctx);               // 8UC3, 8UC1 (a GRAY frame) or 8UC4 (a BGRA / RGBA frame)
+    const uint8_t bg[4] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2], (uint8_t)background[3]};
     {
         hip::ContextLock lock(ctx->mutex());
         if (src.channels() == 1)
             ctx->check(lvk_hip_remap_homography_gray(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, out.rows, out.cols,
                                                      0, 0, H, bg[0]), "remap(homography)");
+        else if (src.channels() == 4)
+            ctx->check(lvk_hip_remap_homography_c4(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, out.rows, out.cols,
+                                                   0, 0, H, bg), "remap(homography)");
         else
         ctx->check(lvk_hip_remap_homography(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, out.rows, out.cols,
                                             0, 0, H, bg, src.format == VideoFrame::YUV ? 1 : 0), "remap(homography)");
@@ -313,7 +320,7 @@ public:
     void apply(const VideoFrame& src, VideoFrame& dst, const cv::Scalar& background = {0, 0, 0}) const
     {
         LVK_HIP_ASSERT(!src.empty());
-        const uint8_t bg[3] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2]};
+        const uint8_t bg[4] = {(uint8_t)background[0], (uint8_t)background[1], (uint8_t)background[2], (uint8_t)background[3]};
         const auto& ctx = src.context();
         VideoFrame out;                                        // dst may be the object src refers to (LCFilter swaps, VSFilter aliases)
         if (m.cols == src.cols && m.rows == src.rows && (size_t)m.cols * m.rows * 8 > 65536)
@@ -333,12 +340,16 @@ public:
         }
         else
         {
-            LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3);
-            out.create(src.size(), src.type(), ctx);           // 8UC3, or 8UC1 (a GRAY frame: lvk_hip_warpmesh_apply_gray, background[0])
+            LVK_HIP_ASSERT(src.channels() == 1 || src.channels() == 3 || src.channels() == 4);
+            // 8UC3, 8UC1 (a GRAY frame: lvk_hip_warpmesh_apply_gray, background[0]) or 8UC4 (a BGRA / RGBA frame: lvk_hip_warpmesh_apply_c4, background[0..3])
+            out.create(src.size(), src.type(), ctx);
             hip::ContextLock lock(ctx->mutex());
             if (src.channels() == 1)
                 ctx->check(lvk_hip_warpmesh_apply_gray(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
                                                        m.off.data(), m.rows, m.cols, bg[0]), "WarpMesh::apply");
+            else if (src.channels() == 4)
+                ctx->check(lvk_hip_warpmesh_apply_c4(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
+                                                     m.off.data(), m.rows, m.cols, bg), "WarpMesh::apply");
             else
             ctx->check(lvk_hip_warpmesh_apply(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step,
                                               m.off.data(), m.rows, m.cols, bg, src.format == VideoFrame::YUV ? 1 : 0), "WarpMesh::apply");

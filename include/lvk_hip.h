@@ -563,6 +563,51 @@ int  lvk_hip_stab_push_gray(lvk_hip_stab* stab, const void* d_frame, int step, i
 int  lvk_hip_stab_push_gray_host(lvk_hip_stab* stab, const void* h_frame, int step, int rows, int cols, uint64_t timestamp,
                                  void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
 
+/* ---- four-channel (8UC4, LVK_FORMAT_BGRA / LVK_FORMAT_RGBA) frames: what game, window and display captures and every source with transparency hand over;
+ * BGRX is a BGRA frame whose fourth byte is carried like alpha ---------------------------------------------------------------------------------------
+ * DEFINITION: in the reference's non-YUV EASU program the twelve tap weights depend on channel 0 alone and each channel is
+ * accumulated, normalised, clamped and converted on its own, so output channel k depends on input channels 0 and k only.  The remap of a four-channel
+ * frame (c0, c1, c2, a) with background (b0, b1, b2, b3) is that program with a fourth channel under the same weights: bytes 0 .. 2 are bit-identical to
+ * the three-channel entry with yuv = 0 on (c0, c1, c2) and background (b0, b1, b2), byte 3 to channel 1 of the three-channel entry with yuv = 0 on
+ * (c0, a, a) and background (b0, b3, b3).  Border, nearest-neighbour (all four bytes copied) and background rules unchanged.  The same for BGRA and RGBA:
+ * the program does not know which of channels 0 and 2 is red.  There is no four-channel YUV format.
+ * The five entries mirror their `_gray` namesakes with FOUR background bytes.  Both frames are 4-byte aligned, both pitches multiples of 4, step >=
+ * 4 * cols, source and destination byte ranges do not overlap: anything else is refused with LVK_HIP_ERR_ARG, the destination untouched.  The kernels are
+ * exact in both remap precisions (no LVK_REMAP_1LSB twins).  A 2 x 2 mesh goes through cv::getPerspectiveTransform and the homography kernel. */
+int lvk_hip_remap_homography_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
+                                void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], const uint8_t bg[4]);
+int lvk_hip_remap_mesh_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step,
+                          const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[4]);
+int lvk_hip_remap_map_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                         const void* d_map, int map_step, const uint8_t bg[4]);
+int lvk_hip_warpmesh_apply_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                              const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[4]);
+int lvk_hip_warpmesh_apply_lens_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                                   const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[4], const lvk_camera_params* lens);
+/* The stabilization filter on four-channel device frames: the contract of the packed-frame push of PART 1 (borrowed frame, *released, overlap mode and
+ * persistent grid, the DELAYED frame emitted at its own size into a d_out of out_rows rows of out_step >= 4 * cols bytes, a push whose output would not
+ * fit refused before anything changes).  format is LVK_FORMAT_BGRA or LVK_FORMAT_RGBA; frame and output are 4-byte aligned with pitches that are multiples
+ * of 4.  The tracker reads cvtColor(..2GRAY) of the colour bytes; the remap is the four-channel one above with background_colour[0..3]: [0..2] are
+ * lvk_stab_settings::background, whose layout is fixed, and [3] is set by lvk_hip_stab_set_background_alpha (0 .. 255; 0 when never set, the fourth value
+ * of the reference's three-value cv::Scalar default; kept across configure()).  The next-output query of PART 1 reports the delayed frame with its own
+ * format: four bytes per pixel.
+ * ONE PIXEL SIZE PER STREAM: a queue holds frames of 1, 3 or 4 bytes per pixel, and every push of another size -- through any entry -- is refused with
+ * LVK_HIP_ERR_ARG before anything changes; so is an RGBA push into a BGRA queue and the reverse.  lvk_hip_stab_restart recovers.  The three-channel entries
+ * keep refusing LVK_FORMAT_BGRA / LVK_FORMAT_RGBA themselves, and lvk_hip_stab_push_obs / _obs_host keep DirectIngest's route for RGBA / BGRA / BGRX.
+ * DECLARED GAPS: the test-mode overlays (draw_trackers, draw_motion_mesh) draw three bytes per pixel and are refused on a four-channel queue; there is
+ * no look-ahead / prefetch for four-channel frames.  stable_region, stabilize_output = 0 and crop_to_stable_region work as for three channels. */
+int  lvk_hip_stab_set_background_alpha(lvk_hip_stab* stab, int alpha);
+int  lvk_hip_stab_push_c4(lvk_hip_stab* stab, const void* d_frame, int step, int rows, int cols, uint64_t timestamp, int format,
+                          void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released,
+                          lvk_frame_info* emitted);
+/* The same push for a frame in PINNED host memory, one plane each way, built as lvk_hip_stab_push_gray_host is: h_frame (any alignment, step >= 4 * cols)
+ * goes up in one copy into a block the library owns until that frame has been emitted, and the four-channel remap stores the emitted frame straight into
+ * oh_out, a pinned plane of out_rows rows of out_step >= 4 * cols bytes, 4-byte aligned, out_step a multiple of 4 (complete after lvk_hip_sync).  Refused
+ * with LVK_HIP_ERR_ARG before anything is uploaded or queued: everything lvk_hip_stab_push_c4 refuses, a pageable input or output plane, frames borrowed
+ * by lvk_hip_stab_push_c4 still queued (and the reverse), and a push while frames announced through lvk_hip_stab_prefetch_yuv420_host are outstanding. */
+int  lvk_hip_stab_push_c4_host(lvk_hip_stab* stab, const void* h_frame, int step, int rows, int cols, uint64_t timestamp, int format,
+                               void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
+
 /* Which schedule the pushes of this filter took so far.  The library picks per push, from what it sees the caller doing (is the bulk stream still
  * busy with the previous remap? did this push begin within 15 us of the last one's return?), between the schedule of a FREE-RUNNING caller
  * (persistent remap grid of 4 blocks per CU next to the tracker, completion through an event) and that of a caller that WAITS for every frame

@@ -49,6 +49,17 @@ _SIG = {
     "lvk_hip_get_remap_precision": (_c.c_int, [_P]),
     "lvk_hip_stab_set_remap_precision": (_c.c_int, [_P, _c.c_int]),
     "lvk_hip_stab_get_remap_precision": (_c.c_int, [_P]),
+    "lvk_hip_remap_homography_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int,
+                                               _c.c_int, _c.c_int, _c.POINTER(_c.c_float), _c.POINTER(_c.c_uint8)]),
+    "lvk_hip_remap_mesh_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.POINTER(_c.c_uint8)]),
+    "lvk_hip_remap_map_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_uint8)]),
+    "lvk_hip_warpmesh_apply_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.POINTER(_c.c_uint8)]),
+    "lvk_hip_warpmesh_apply_lens_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_float), _c.c_int, _c.c_int, _c.POINTER(_c.c_uint8), _P]),
+    "lvk_hip_stab_set_background_alpha": (_c.c_int, [_P, _c.c_int]),
+    "lvk_hip_stab_push_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_uint64, _c.c_int, _P, _c.c_int, _c.c_int,
+                                        _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _c.POINTER(_P), _P]),
+    "lvk_hip_stab_push_c4_host": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_uint64, _c.c_int, _P, _c.c_int, _c.c_int,
+                                             _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _P]),
     "lvk_hip_upscale": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_sharpen": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
     "lvk_hip_native_rcp": (_c.c_int, [_P, _P, _P, _c.c_size_t]),

@@ -20,6 +20,11 @@ def _u8x3(bg):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
 
+def _u8x4(bg):
+    a = np.ascontiguousarray(bg, dtype=np.uint8).reshape(4)
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
 TRACK_CHAIN_GUARD = 64        # LVK_TRACK_CHAIN_GUARD: entries in front of and behind the flow kernel's output buffers
 TRACK_CHAIN_FILL = 0xA5       # LVK_TRACK_CHAIN_FILL: every output byte no kernel wrote
 
@@ -189,6 +194,61 @@ class Context:
         else:
             arr = (ctypes.c_double * 9)(*[float(v) for v in lens])
             self._check(self.lib.lvk_hip_warpmesh_apply_lens_gray(*args, arr))
+        return out
+
+    # ---- four-channel (BGRA / RGBA) frames: the non-YUV EASU program with a fourth channel under the same weights; src / out: torch uint8
+    # [rows, cols, 4], 4-byte aligned, pitches multiples of 4; bg: four bytes ------------------------------------------------------------
+    def _c4_out(self, src, out, shape=None):
+        import torch
+        if src.dim() != 3 or src.shape[2] != 4:
+            raise ValueError("a four-channel frame is a [rows, cols, 4] uint8 tensor")
+        return out if out is not None else torch.empty((shape or tuple(src.shape[:2])) + (4,), dtype=torch.uint8, device=src.device)
+
+    def remap_homography_c4(self, src, H, bg=(255, 0, 255, 255), out=None, dst_size=None, offset=(0, 0)):
+        """lvk_hip_remap_homography_c4: remap_homography for a four-channel frame, four background bytes."""
+        rows, cols = src.shape[:2]
+        drows, dcols = dst_size if dst_size is not None else (rows, cols)
+        out = self._c4_out(src, out, (drows, dcols))
+        Ha, Hp = _f32(np.asarray(H, dtype=np.float32).reshape(9))
+        bga, bgp = _u8x4(bg)
+        self._check(self.lib.lvk_hip_remap_homography_c4(self.handle, src.data_ptr(), src.stride(0), rows, cols, out.data_ptr(), out.stride(0), drows, dcols,
+                                                         offset[0], offset[1], Hp, bgp))
+        return out
+
+    def remap_mesh_c4(self, src, mesh, bg=(255, 0, 255, 255), out=None):
+        """lvk_hip_remap_mesh_c4: remap_mesh for a four-channel frame."""
+        out = self._c4_out(src, out)
+        ma, mp = _f32(mesh)
+        bga, bgp = _u8x4(bg)
+        self._check(self.lib.lvk_hip_remap_mesh_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
+                                                   mp, ma.shape[0], ma.shape[1], bgp))
+        return out
+
+    def remap_map_c4(self, src, offsets, bg=(255, 0, 255, 255), out=None):
+        """lvk_hip_remap_map_c4: remap_map for a four-channel frame (offsets: torch float32 [rows, cols, 2] on the GPU, pixels)."""
+        out = self._c4_out(src, out)
+        bga, bgp = _u8x4(bg)
+        self._check(self.lib.lvk_hip_remap_map_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
+                                                  offsets.data_ptr(), offsets.stride(0) * 4, bgp))
+        return out
+
+    def warpmesh_apply_c4(self, src, mesh, bg=(255, 0, 255, 255), out=None):
+        """lvk_hip_warpmesh_apply_c4: WarpMesh::apply on a four-channel frame."""
+        out = self._c4_out(src, out)
+        ma, mp = _f32(mesh)
+        bga, bgp = _u8x4(bg)
+        self._check(self.lib.lvk_hip_warpmesh_apply_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
+                                                       mp, ma.shape[0], ma.shape[1], bgp))
+        return out
+
+    def warpmesh_apply_lens_c4(self, src, mesh, lens, bg=(255, 0, 255, 255), out=None):
+        """lvk_hip_warpmesh_apply_lens_c4: the lens pre-warp (camera params) fused into WarpMesh::apply on a four-channel frame."""
+        out = self._c4_out(src, out)
+        ma, mp = _f32(mesh)
+        bga, bgp = _u8x4(bg)
+        arr = (ctypes.c_double * 9)(*[float(v) for v in lens])
+        self._check(self.lib.lvk_hip_warpmesh_apply_lens_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
+                                                            mp, ma.shape[0], ma.shape[1], bgp, arr))
         return out
 
     # ---- a3/a4/a7 image ops --------------------------------------------------------------------------

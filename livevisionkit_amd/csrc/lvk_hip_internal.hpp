@@ -398,6 +398,17 @@ int lvk_launch_remap_map_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step,
 int lvk_launch_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
                                         const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const RemapLaunch& o);
 
+// Dense remap of four-channel (8UC4) frames (remap_c4.hip): the non-YUV EASU program with a fourth channel under the same weights; bg = the four background
+// bytes.  Both planes 4-byte aligned with pitches that are multiples of 4.
+int lvk_launch_remap_homography_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
+                                   void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], const uint8_t bg[4], const RemapLaunch& o);
+int lvk_launch_remap_mesh_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                             const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[4], const RemapLaunch& o);
+int lvk_launch_remap_map_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
+                            void* d_dst, int dst_step, const void* d_map, int map_step, const uint8_t bg[4], const RemapLaunch& o);   // no lens, full grid
+int lvk_launch_warpmesh_apply_lens_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
+                                      const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[4], const RemapLaunch& o);
+
 // Debug overlays (draw.hip)
 int lvk_launch_draw_grid(lvk_hip_ctx* ctx, hipStream_t stream, void* d_dst, int dst_step, int rows, int cols, int grid_w, int grid_h,
                          const uint8_t colour[3], int thickness);

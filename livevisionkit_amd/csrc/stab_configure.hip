@@ -447,6 +447,15 @@ int lvk_hip_stab_set_remap_precision(lvk_hip_stab* st, int precision)
 
 int lvk_hip_stab_get_remap_precision(const lvk_hip_stab* st) { return st ? st->remap_precision : LVK_HIP_ERR_ARG; }
 
+// background_colour[3] for four-channel frames, from the next emitted frame on (emit() reads it at its launch; nothing else changes)
+int lvk_hip_stab_set_background_alpha(lvk_hip_stab* st, int alpha)
+{
+    if (!st) return LVK_HIP_ERR_ARG;
+    if (alpha < 0 || alpha > 255) return st->ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_set_background_alpha: a byte, 0 .. 255");
+    st->background_alpha = (uint8_t)alpha;
+    return LVK_HIP_OK;
+}
+
 // Per-stage GPU time measured with HIP events on the launch stream.  enable != 0 starts (and resets) the
 // accumulation; lvk_hip_stab_get_profile synchronises the stream and reports, per stage, the summed milliseconds
 // and the number of timed launches (stage ids: LVK_STAGE_*).
@@ -501,6 +510,7 @@ int lvk_hip_stab_draw_trackers(lvk_hip_stab* st)
     st->finish_post();
     const QueuedFrame& f = st->queue.back();
     if (f.format == LVK_FORMAT_GRAY) return st->fail(LVK_HIP_ERR_ARG, "draw_trackers: the overlay kernels draw three bytes per pixel; a GRAY queue is refused (nothing was drawn)");
+    if (lvk_format_channels(f.format) == 4) return st->fail(LVK_HIP_ERR_ARG, "draw_trackers: the overlay kernels draw three bytes per pixel; a four-channel queue is refused (nothing was drawn)");
     double r[3], g[3], b[3];
     overlay_colours(f.format, r, g, b);
     uint8_t col[3];
@@ -520,6 +530,7 @@ int lvk_hip_stab_draw_motion_mesh(lvk_hip_stab* st)
     LVK_HIP_REQUIRE(st->ctx, !st->queue.empty());
     const QueuedFrame& f = st->queue.back();
     if (f.format == LVK_FORMAT_GRAY) return st->fail(LVK_HIP_ERR_ARG, "draw_motion_mesh: the overlay kernels draw three bytes per pixel; a GRAY queue is refused (nothing was drawn)");
+    if (lvk_format_channels(f.format) == 4) return st->fail(LVK_HIP_ERR_ARG, "draw_motion_mesh: the overlay kernels draw three bytes per pixel; a four-channel queue is refused (nothing was drawn)");
     double r[3], g[3], b[3];
     overlay_colours(f.format, r, g, b);
     const uint8_t col[3] = {(uint8_t)b[0], (uint8_t)b[1], (uint8_t)b[2]};

@@ -429,33 +429,37 @@ int lvk_hip_stab_push_obs_host(lvk_hip_stab* st, int video_format, const void* c
     return LVK_HIP_OK;
 }
 
-// The host entry for ONE-channel frames (Y800 / VideoFrame::GRAY): lvk_hip_stab_push_gray with the plane in pinned host memory, one plane each way.
+// The host entries for ONE packed plane of 1 (Y800 / VideoFrame::GRAY) or 4 (BGRA / RGBA) bytes per pixel: lvk_hip_stab_push_gray / lvk_hip_stab_push_c4 with
+// the plane in pinned host memory, one plane each way.
 //   in:  one copy on the upload stream into a block of the context's pool that the entry owns until its frame has been emitted (the queue holds whole
 //        frames); the tracker's stream waits for the copy's event; the host plane is the caller's again when the call returns;
-//   out: the one-channel remap stores into the caller's pinned plane itself (no download route).
-// Refused before anything is uploaded or queued: what lvk_hip_stab_push_gray refuses (sizes, a short step, the other format class in the queue, an output
-// plane that does not hold the DELAYED frame), frames that lvk_hip_stab_push_gray borrowed still queued, pageable planes, outstanding 4:2:0 look-ahead.
-int lvk_hip_stab_push_gray_host(lvk_hip_stab* st, const void* h_frame, int step, int rows, int cols, uint64_t timestamp,
-                                void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted)
+//   out: the remap stores into the caller's pinned plane itself (no download route).
+// Refused before anything is uploaded or queued: what the device entry refuses (sizes, a short step, another pixel size in the queue, an output plane that
+// does not hold the DELAYED frame), frames that the device entry borrowed still queued, pageable planes, outstanding 4:2:0 look-ahead.
+static int lvk_stab_push_plain_host(lvk_hip_stab* st, int bpp, int format, const void* h_frame, int step, int rows, int cols, uint64_t timestamp,
+                                    void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted)
 {
     if (!st) return LVK_HIP_ERR_ARG;
     if (produced) *produced = 0;
+    const std::string name_s = bpp == 1 ? "lvk_hip_stab_push_gray_host" : "lvk_hip_stab_push_c4_host";
+    const char* name = name_s.c_str();
     lvk_device_guard device_guard(st->ctx);
     lvk_hip_ctx* ctx = st->ctx;
-    LVK_HIP_REQUIRE(ctx, h_frame && rows > 0 && cols > 0 && step >= cols);
+    LVK_HIP_REQUIRE(ctx, h_frame && rows > 0 && cols > 0 && step >= bpp * cols);
     if (!st->buffers_ok) return ctx->fail(LVK_HIP_ERR_RUNTIME, "the last configure() failed while allocating the tracker's buffers: configure again");
     int rc;
     QueuedFrame due{}; bool will_emit = false;
-    if ((rc = lvk_stab_check_gray(st, true, rows, cols, timestamp, oh_out, out_step, out_rows, &due, &will_emit)) != LVK_HIP_OK) return rc;
+    // (the host plane is copied into a packed block of the library's own: only the output plane, which the remap writes, has an alignment rule)
+    if ((rc = lvk_stab_check_plain(st, true, bpp, format, nullptr, 0, rows, cols, timestamp, oh_out, out_step, out_rows, &due, &will_emit)) != LVK_HIP_OK) return rc;
     if (!st->hostio.ahead.empty())
-        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_gray_host: frames announced through lvk_hip_stab_prefetch_yuv420_host have not been pushed yet -- push them "
-                                         "or lvk_hip_stab_prefetch_cancel() first; nothing was queued");
-    const HostPlane in{h_frame, step, cols, rows};
-    if ((rc = st->require_pinned_planes(&in, 1, "lvk_hip_stab_push_gray_host")) != LVK_HIP_OK) return rc;
-    if (oh_out && out_step >= (will_emit ? due.cols : cols) && out_rows >= (will_emit ? due.rows : rows))
+        return st->fail(LVK_HIP_ERR_ARG, name_s + ": frames announced through lvk_hip_stab_prefetch_yuv420_host have not been pushed yet -- push them "
+                                                  "or lvk_hip_stab_prefetch_cancel() first; nothing was queued");
+    const HostPlane in{h_frame, step, bpp * cols, rows};
+    if ((rc = st->require_pinned_planes(&in, 1, name)) != LVK_HIP_OK) return rc;
+    if (oh_out && out_step >= bpp * (will_emit ? due.cols : cols) && out_rows >= (will_emit ? due.rows : rows))
     {
-        const HostPlane out{oh_out, out_step, will_emit ? due.cols : cols, will_emit ? due.rows : rows};
-        if ((rc = st->require_pinned_planes(&out, 1, "lvk_hip_stab_push_gray_host (output)")) != LVK_HIP_OK) return rc;
+        const HostPlane out{oh_out, out_step, bpp * (will_emit ? due.cols : cols), will_emit ? due.rows : rows};
+        if ((rc = st->require_pinned_planes(&out, 1, (name_s + " (output)").c_str())) != LVK_HIP_OK) return rc;
     }
     // blocks whose frame left the queue outside a push (restart, a shrinking queue): nothing may still read them
     {
@@ -476,14 +480,15 @@ int lvk_hip_stab_push_gray_host(lvk_hip_stab* st, const void* h_frame, int step,
     if (!st->gray_up_done) LVK_HIP_CHECK(ctx, hipEventCreateWithFlags(&st->gray_up_done, hipEventDisableTiming));
     if (!st->gray_fence) LVK_HIP_CHECK(ctx, hipEventCreateWithFlags(&st->gray_fence, hipEventDisableTiming));
     void* d_frame = nullptr;
-    if ((rc = lvk_hip_malloc(ctx, (size_t)rows * cols, &d_frame)) != LVK_HIP_OK) return rc;
+    const size_t row_bytes = (size_t)bpp * cols;
+    if ((rc = lvk_hip_malloc(ctx, row_bytes * rows, &d_frame)) != LVK_HIP_OK) return rc;
     // the block may have been read last by a remap on the tracking stream that has not run yet (no overlap: a frame is released as soon as its remap is
     // enqueued): the upload follows whatever that stream holds.  In overlap mode a frame is released only after its remap has finished.
     hipStream_t up = st->hostio.up;
     hipError_t e = hipEventRecord(st->gray_fence, ctx->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(up, st->gray_fence, 0);
-    if (e == hipSuccess) e = step == cols ? hipMemcpyAsync(d_frame, h_frame, (size_t)rows * cols, hipMemcpyHostToDevice, up)
-                                          : hipMemcpy2DAsync(d_frame, (size_t)cols, h_frame, (size_t)step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = (size_t)step == row_bytes ? hipMemcpyAsync(d_frame, h_frame, row_bytes * rows, hipMemcpyHostToDevice, up)
+                                                       : hipMemcpy2DAsync(d_frame, row_bytes, h_frame, (size_t)step, row_bytes, (size_t)rows, hipMemcpyHostToDevice, up);
     if (e == hipSuccess) e = hipEventRecord(st->gray_up_done, up);
     if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, st->gray_up_done, 0);
     if (e != hipSuccess) { (void)hipStreamSynchronize(up); (void)lvk_hip_free(ctx, d_frame); return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(e)); }
@@ -493,7 +498,8 @@ int lvk_hip_stab_push_gray_host(lvk_hip_stab* st, const void* h_frame, int step,
     st->gray_host_entry_now = true;
     st->host_direct_now = will_emit;                               // the remap's stores cross the host link
     int prod = 0; const void* released = nullptr;
-    rc = lvk_hip_stab_push_gray(st, d_frame, cols, rows, cols, timestamp, oh_out, out_step, out_rows, &prod, out_timestamp, &released, emitted);
+    rc = bpp == 1 ? lvk_hip_stab_push_gray(st, d_frame, cols, rows, cols, timestamp, oh_out, out_step, out_rows, &prod, out_timestamp, &released, emitted)
+                  : lvk_hip_stab_push_c4(st, d_frame, 4 * cols, rows, cols, timestamp, format, oh_out, out_step, out_rows, &prod, out_timestamp, &released, emitted);
     const hipError_t se = hipEventSynchronize(st->gray_up_done);    // "consumed on return": the host plane is the caller's again
     auto drop = [&](const void* p) {
         auto it = std::find(st->gray_host_live.begin(), st->gray_host_live.end(), p);
@@ -506,6 +512,22 @@ int lvk_hip_stab_push_gray_host(lvk_hip_stab* st, const void* h_frame, int step,
     if (produced) *produced = prod;
     st->hostio.last_end = std::chrono::steady_clock::now();
     return LVK_HIP_OK;
+}
+
+int lvk_hip_stab_push_gray_host(lvk_hip_stab* st, const void* h_frame, int step, int rows, int cols, uint64_t timestamp,
+                                void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted)
+{
+    return lvk_stab_push_plain_host(st, 1, LVK_FORMAT_GRAY, h_frame, step, rows, cols, timestamp, oh_out, out_step, out_rows, produced, out_timestamp, emitted);
+}
+
+int lvk_hip_stab_push_c4_host(lvk_hip_stab* st, const void* h_frame, int step, int rows, int cols, uint64_t timestamp, int format,
+                              void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted)
+{
+    if (!st) return LVK_HIP_ERR_ARG;
+    if (produced) *produced = 0;
+    if (format != LVK_FORMAT_BGRA && format != LVK_FORMAT_RGBA)
+        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_c4_host: format is LVK_FORMAT_BGRA or LVK_FORMAT_RGBA; nothing was queued");
+    return lvk_stab_push_plain_host(st, 4, format, h_frame, step, rows, cols, timestamp, oh_out, out_step, out_rows, produced, out_timestamp, emitted);
 }
 
 // Pinned host memory for the planes of lvk_hip_stab_push_yuv420_host (what obs_source_frame buffers would be registered as)

@@ -187,6 +187,9 @@ struct lvk_hip_stab
     // lvk_hip_stab_set_remap_precision: the kernels of the three-channel output remap, read by emit() at every launch (the GRAY remap is exact in both);
     // a stabilizer is created EXACT whatever its context's setting
     int remap_precision = LVK_REMAP_EXACT;
+    // lvk_hip_stab_set_background_alpha: the fourth background byte of the four-channel remap (lvk_stab_settings::background has three values and the
+    // struct's layout is the ABI's); 0 = cv::Scalar's fourth value of the reference's three-value default.  Not part of the settings: configure() keeps it.
+    uint8_t background_alpha = 0;
 
     // ---- optional overlap of the output remap with the next frame's tracking (second stream)
     bool overlap = false;
@@ -304,12 +307,12 @@ struct lvk_hip_stab
         std::chrono::steady_clock::time_point last_end{};      // when the previous host push returned
     } hostio;
     bool host_free_running_hint = false;                 // lvk_hip_stab_push_yuv420_host's own finding, for the push it wraps
-    // lvk_hip_stab_push_gray_host: the one-channel frames it uploaded and still owns (queued, or waiting for their remap), from the context's block pool;
+    // lvk_hip_stab_push_gray_host / lvk_hip_stab_push_c4_host (one queue holds frames of one of them only): the frames the entry uploaded and still owns (queued, or waiting for their remap), from the context's block pool;
     // the event of the newest upload, and the fence that keeps the upload stream from writing a block a remap may still read
     std::vector<void*> gray_host_live;
     hipEvent_t gray_up_done = nullptr, gray_fence = nullptr;
     bool gray_host_owns(const void* p) const { return std::find(gray_host_live.begin(), gray_host_live.end(), p) != gray_host_live.end(); }
-    bool gray_host_entry_now = false;                     // lvk_hip_stab_push_gray_host is wrapping the push that runs
+    bool gray_host_entry_now = false;                     // one of the two host entries is wrapping the push that runs
     void free_gray_host();
     bool host_direct_now = false;                        // the push being wrapped writes its output planes straight into host memory
     hipEvent_t ingest_wait[2] = {nullptr, nullptr};      // events the newest frame's 4:2:0 conversion waits for (the plane uploads), or nullptr
@@ -415,13 +418,15 @@ int lvk_stab_check_in_planes(lvk_hip_stab* st, int vf, const void* const in_plan
 int lvk_stab_check_due(lvk_hip_stab* st, int vf, int frame_format, int rows, int cols, uint64_t timestamp, void* const op[3], const int os[3], int o_rows,
                        lvkstab::QueuedFrame* due, bool* will_emit);
 
-// What the GRAY entries refuse before anything changes (stabilizer.hip): frames of the other format class or of the other GRAY entry in the queue, and an
-// output buffer that does not hold the frame this push emits; *due / *will_emit as for lvk_stab_check_due.  host: the caller is lvk_hip_stab_push_gray_host.
-int lvk_stab_check_gray(lvk_hip_stab* st, bool host, int rows, int cols, uint64_t timestamp, const void* d_out, int out_step, int out_rows,
-                        lvkstab::QueuedFrame* due, bool* will_emit);
+// What the entries for one packed plane of `bpp` = 1 (GRAY) or 4 (BGRA / RGBA) bytes per pixel refuse before anything changes (stabilizer.hip): frames of
+// another pixel size (or, for four channels, of the other format) or of the entry's host / device twin in the queue, pool frames in the queue, a
+// four-channel frame or output that is not 4-byte aligned with a pitch that is a multiple of 4, and an output buffer that does not hold the frame this
+// push emits; *due / *will_emit as for lvk_stab_check_due.  host: the caller is the `_host` entry.
+int lvk_stab_check_plain(lvk_hip_stab* st, bool host, int bpp, int format, const void* d_frame, int step, int rows, int cols, uint64_t timestamp,
+                         const void* d_out, int out_step, int out_rows, lvkstab::QueuedFrame* due, bool* will_emit);
 
 // StabilizationFilter::filter (stabilizer.hip); the entry points of the other units wrap it
 int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows, int cols, uint64_t timestamp, int format,
                        const void* luma, int luma_step, int luma_pix,
                        void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released,
-                       lvkstab::OutPlanes420* o420 = nullptr, lvk_frame_info* emitted = nullptr, bool gray_entry = false);
+                       lvkstab::OutPlanes420* o420 = nullptr, lvk_frame_info* emitted = nullptr, int bpp = 3);      // bpp: bytes per pixel of the queue this push joins (1, 3 or 4)

@@ -367,6 +367,7 @@ int lvk_hip_stab::track(const QueuedFrame& f, const void* luma, int luma_step, i
 }
 
 static const char* lvk_frame_format_name(int f);
+static std::string lvk_stab_pixel_class_clash(const lvk_hip_stab* st, int bpp, int format);
 
 // StabilizationFilter::filter (StabilizationFilter.cpp:69-135).  (luma, luma_step, luma_pix): where the tracker reads the
 // luma of this frame from -- the packed frame itself (pix 3) or, on the YUV420 path, the caller's planar Y (pix 1).
@@ -374,28 +375,30 @@ static const char* lvk_frame_format_name(int f);
 int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows, int cols, uint64_t timestamp, int format,
                      const void* luma, int luma_step, int luma_pix,
                      void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released, OutPlanes420* o420,
-                     lvk_frame_info* emitted, bool gray_entry)
+                     lvk_frame_info* emitted, int bpp)
 {
     lvk_hip_ctx* ctx = st->ctx;
     if (produced) *produced = 0;
     if (released) *released = nullptr;
-    // bytes per pixel of this push's frames: the GRAY entries (lvk_hip_stab_push_gray*) queue one-channel frames, every other entry three-channel ones
-    const int bpp = gray_entry ? 1 : 3;
+    // bpp, bytes per pixel of this push's frames: the GRAY entries (lvk_hip_stab_push_gray*) queue one-channel frames, the four-channel entries
+    // (lvk_hip_stab_push_c4*) BGRA / RGBA frames, every other entry three-channel ones
+    LVK_HIP_REQUIRE(ctx, bpp == 1 || bpp == 3 || bpp == 4);
+    const bool gray_entry = bpp == 1, c4_entry = bpp == 4;
     if (gray_entry) LVK_HIP_REQUIRE(ctx, d_frame && rows > 0 && cols > 0 && step >= cols && format == LVK_FORMAT_GRAY && luma_pix == 1);
+    else if (c4_entry) LVK_HIP_REQUIRE(ctx, d_frame && rows > 0 && cols > 0 && step >= 4 * cols && (format == LVK_FORMAT_BGRA || format == LVK_FORMAT_RGBA) && luma_pix == 4);
     else LVK_HIP_REQUIRE(ctx, d_frame && rows > 0 && cols > 0 && step >= 3 * cols);           // !input.empty()
     if (!st->buffers_ok) return ctx->fail(LVK_HIP_ERR_RUNTIME, "the last configure() failed while allocating the tracker's buffers: configure again");
     // 3-channel VideoFrame formats (VideoFrame.cpp:170-306): YUV tracks channel 0, BGR / RGB track cvtColor(..2GRAY); the remap
-    // runs the YUV or the RGB EASU program by the frame's format (Image.cpp:36-41).  4-channel frames are not on this path; GRAY frames -- their own
-    // luma, remapped by the one-channel kernels (remap_gray.hip) -- only through the GRAY entries.
-    if (!gray_entry) LVK_HIP_REQUIRE(ctx, format == LVK_FORMAT_YUV || format == LVK_FORMAT_BGR || format == LVK_FORMAT_RGB);
-    const int luma_channel = (gray_entry || format == LVK_FORMAT_YUV) ? 0 : (format == LVK_FORMAT_BGR ? -1 : -2);
-    if (!gray_entry) LVK_HIP_REQUIRE(ctx, luma_pix == 3 || format == LVK_FORMAT_YUV);
-    // One format class per stream, like the plane entries (lvk_stab_check_due): the emitted frame leaves through THIS push's output buffer, whose pixel size is
-    // that of this push's class -- a queue that holds three-channel frames refuses a GRAY push and the reverse, before anything changes; restart() recovers.
-    for (const QueuedFrame& q : st->queue)
-        if ((q.format == LVK_FORMAT_GRAY) != gray_entry)
-            return ctx->fail(LVK_HIP_ERR_ARG, std::string("a frame of this stream was queued as ") + lvk_frame_format_name(q.format) + " and this push's frame is " +
-                                                  lvk_frame_format_name(format) + ": one-channel and three-channel frames do not share a queue -- restart() before switching; nothing was queued");
+    // runs the YUV or the RGB EASU program by the frame's format (Image.cpp:36-41).  GRAY frames -- their own luma, remapped by the one-channel kernels
+    // (remap_gray.hip) -- come only through the GRAY entries; BGRA / RGBA frames -- tracked as cvtColor(..2GRAY) of their colour bytes, remapped by the
+    // four-channel kernels (remap_c4.hip) -- only through the four-channel entries.
+    if (bpp == 3) LVK_HIP_REQUIRE(ctx, format == LVK_FORMAT_YUV || format == LVK_FORMAT_BGR || format == LVK_FORMAT_RGB);
+    const int luma_channel = (gray_entry || format == LVK_FORMAT_YUV) ? 0 : ((format == LVK_FORMAT_BGR || format == LVK_FORMAT_BGRA) ? -1 : -2);
+    if (bpp == 3) LVK_HIP_REQUIRE(ctx, luma_pix == 3 || format == LVK_FORMAT_YUV);
+    // One pixel size per stream, like the plane entries (lvk_stab_check_due): the emitted frame leaves through THIS push's output buffer, whose pixel size is
+    // that of this push's class -- a queue that holds frames of 1, 3 or 4 bytes per pixel refuses a push of another size, and a BGRA queue an RGBA push and
+    // the reverse (the output carries one format), before anything changes; restart() recovers.
+    { const std::string why = lvk_stab_pixel_class_clash(st, bpp, format); if (!why.empty()) return ctx->fail(LVK_HIP_ERR_ARG, why); }
     const QueuedFrame in{d_frame, step, rows, cols, timestamp, format};
     // The frame this push will emit is the DELAYED one, at its own size (the queue holds whole frames, StabilizationFilter.cpp:118-131; dst is
     // allocated from the delayed source, WarpMesh.cpp:183-223 -> Image.cpp:53,116): what cannot be written is refused HERE, before the tracker
@@ -431,7 +434,7 @@ int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows
     st->sched[st->caller_runs_free ? LVK_SCHED_PUSH_FREE_RUNNING : LVK_SCHED_PUSH_SYNCHRONISED]++;
     { const int lrc = st->ensure_lens(rows, cols); if (lrc != LVK_HIP_OK) return lrc; }
     static const WarpMeshF identity_mesh(2, 2);
-    const uint8_t bg[3] = {(uint8_t)st->s.background[0], (uint8_t)st->s.background[1], (uint8_t)st->s.background[2]};
+    const uint8_t bg[4] = {(uint8_t)st->s.background[0], (uint8_t)st->s.background[1], (uint8_t)st->s.background[2], st->background_alpha};      // [3]: lvk_hip_stab_set_background_alpha (four-channel frames only)
 
     auto enqueue = [&]() {
         if (st->queue.size() == st->queue_capacity) { if (released) *released = st->queue.front().d_ptr; st->queue.pop_front(); }
@@ -483,6 +486,7 @@ int lvk_stab_push_impl(lvk_hip_stab* st, const void* d_frame, int step, int rows
             o420->used = true;
         }
         else if (mesh && gray_entry) rc = lvk_launch_warpmesh_apply_lens_gray(ctx, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg[0], how);
+        else if (mesh && c4_entry) rc = lvk_launch_warpmesh_apply_lens_c4(ctx, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg, how);
         else if (mesh) rc = lvk_launch_warpmesh_apply_lens(ctx, f.d_ptr, f.step, f.rows, f.cols, d_out, out_step, mesh->off.data(), mesh->rows, mesh->cols, bg,
                                                       f.format == LVK_FORMAT_YUV ? 1 : 0, how);
         else
@@ -727,27 +731,66 @@ int lvk_stab_check_due(lvk_hip_stab* st, int vf, int frame_format, int rows, int
     return LVK_HIP_OK;
 }
 
-int lvk_stab_check_gray(lvk_hip_stab* st, bool host, int rows, int cols, uint64_t timestamp, const void* d_out, int out_step, int out_rows,
-                        lvkstab::QueuedFrame* due_out, bool* will_emit_out)
+// empty, or why a push of `bpp`-byte pixels of `format` may not join the queue
+static std::string lvk_stab_pixel_class_clash(const lvk_hip_stab* st, int bpp, int format)
 {
-    if (!st->queue.empty() && st->queue_kind == 2)
-        return st->fail(LVK_HIP_ERR_ARG, "frames of lvk_hip_stab_push_yuv420 / lvk_hip_stab_push_obs are still queued: restart() before switching to a GRAY push; nothing was queued");
     for (const QueuedFrame& q : st->queue)
-    {
-        if (q.format != LVK_FORMAT_GRAY)
-            return st->fail(LVK_HIP_ERR_ARG, std::string("a frame of this stream was queued as ") + lvk_frame_format_name(q.format) + " and this push's frame is GRAY"
-                                                 ": one-channel and three-channel frames do not share a queue -- restart() before switching; nothing was queued");
+        if (lvk_format_channels(q.format) != bpp || (bpp == 4 && q.format != format))
+            return std::string("a frame of this stream was queued as ") + lvk_frame_format_name(q.format) + " and this push's frame is " + lvk_frame_format_name(format) +
+                   ": one-channel, three-channel and four-channel frames (and BGRA and RGBA frames) do not share a queue -- restart() before switching; nothing was queued";
+    return std::string();
+}
+
+int lvk_stab_check_plain(lvk_hip_stab* st, bool host, int bpp, int format, const void* d_frame, int step, int rows, int cols, uint64_t timestamp,
+                         const void* d_out, int out_step, int out_rows, lvkstab::QueuedFrame* due_out, bool* will_emit_out)
+{
+    const char* name = bpp == 1 ? "lvk_hip_stab_push_gray" : "lvk_hip_stab_push_c4";
+    if (!st->queue.empty() && st->queue_kind == 2)
+        return st->fail(LVK_HIP_ERR_ARG, std::string("frames of lvk_hip_stab_push_yuv420 / lvk_hip_stab_push_obs are still queued: restart() before switching to ") + name + "; nothing was queued");
+    { const std::string why = lvk_stab_pixel_class_clash(st, bpp, format); if (!why.empty()) return st->fail(LVK_HIP_ERR_ARG, why); }
+    for (const QueuedFrame& q : st->queue)
         if (st->gray_host_owns(q.d_ptr) != host)
-            return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_gray borrows its frames and lvk_hip_stab_push_gray_host owns them: restart() before switching between the two; nothing was queued");
-    }
+            return st->fail(LVK_HIP_ERR_ARG, std::string(name) + " borrows its frames and " + name + "_host owns them: restart() before switching between the two; nothing was queued");
+    // the four-channel kernels address a pixel as a dword: what they would refuse at the emit is refused here, before the frame is queued
+    const auto dword_plane = [](const void* p, int pitch) { return ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)pitch) & 3u) == 0; };
+    if (bpp == 4 && !dword_plane(d_frame, step))
+        return st->fail(LVK_HIP_ERR_ARG, std::string(name) + ": a four-channel frame is 4-byte aligned and its pitch a multiple of 4; nothing was queued");
     QueuedFrame due{};
-    const bool will_emit = rows > 0 && cols > 0 && st->next_output(QueuedFrame{nullptr, cols, rows, cols, timestamp, LVK_FORMAT_GRAY}, &due);
-    if (will_emit && !(d_out != nullptr && out_step >= due.cols && out_rows >= due.rows))
+    const bool will_emit = rows > 0 && cols > 0 && st->next_output(QueuedFrame{nullptr, bpp * cols, rows, cols, timestamp, format}, &due);
+    if (will_emit && !(d_out != nullptr && out_step >= bpp * due.cols && out_rows >= due.rows && (bpp != 4 || dword_plane(d_out, out_step))))
         return st->fail(LVK_HIP_ERR_ARG, "the output buffer does not hold the frame this push emits: " + std::to_string(due.cols) + " x " + std::to_string(due.rows) +
-                                             " (the DELAYED frame's own size -- lvk_hip_stab_next_output); nothing was queued");
+                                             " (the DELAYED frame's own size -- lvk_hip_stab_next_output" + (bpp == 4 ? "; 4-byte aligned, pitch a multiple of 4" : "") + "); nothing was queued");
     if (due_out) *due_out = due;
     if (will_emit_out) *will_emit_out = will_emit;
     return LVK_HIP_OK;
+}
+
+// The push of the entries that borrow ONE packed plane of 1 or 4 bytes per pixel (lvk_hip_stab_push_gray, lvk_hip_stab_push_c4): borrowed frames, the size
+// rule, overlap and *released as for lvk_hip_stab_push; a queue holds frames of one pixel size only.
+static int lvk_stab_push_plain(lvk_hip_stab* st, int bpp, int format, const void* d_frame, int step, int rows, int cols, uint64_t timestamp,
+                               void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released, lvk_frame_info* emitted)
+{
+    lvk_device_guard device_guard(st->ctx);
+    st->trace.begin();
+    st->prof_tick++;
+    st->push_seq++;
+    struct AnnouncementEnds { lvk_hip_stab* s; ~AnnouncementEnds() { s->ahead_announced = lvk_hip_stab::LumaAhead(); } } announcement_ends{st};
+    if (produced) *produced = 0;
+    if (released) *released = nullptr;
+    // (the queue's owner and format class are checked before queue_kind / pool_frames are written: a refused push leaves everything as it was)
+    int rc = lvk_stab_check_plain(st, st->gray_host_entry_now, bpp, format, d_frame, step, rows, cols, timestamp, d_out, out_step, out_rows, nullptr, nullptr);
+    if (rc != LVK_HIP_OK) return rc;
+    if (st->queue.empty()) st->queue_kind = 0;
+    st->queue_kind = 1;
+    st->pool_frames = false;
+    rc = st->mark_caller_work();
+    if (rc != LVK_HIP_OK) return rc;
+    rc = lvk_stab_push_impl(st, d_frame, step, rows, cols, timestamp, format, d_frame, step, bpp, d_out, out_step, out_rows, produced, out_timestamp, released, nullptr,
+                            emitted, bpp);
+    if (released && !*released && !st->orphaned.empty()) { *released = st->orphaned.front(); st->orphaned.pop_front(); }
+    st->trace.mark(HostTrace::EXIT);
+    st->last_push_end = std::chrono::steady_clock::now();
+    return rc;
 }
 
 extern "C" {
@@ -790,27 +833,20 @@ int lvk_hip_stab_push_gray(lvk_hip_stab* st, const void* d_frame, int step, int 
                            void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released, lvk_frame_info* emitted)
 {
     if (!st) return LVK_HIP_ERR_ARG;
-    lvk_device_guard device_guard(st->ctx);
-    st->trace.begin();
-    st->prof_tick++;
-    st->push_seq++;
-    struct AnnouncementEnds { lvk_hip_stab* s; ~AnnouncementEnds() { s->ahead_announced = lvk_hip_stab::LumaAhead(); } } announcement_ends{st};
+    return lvk_stab_push_plain(st, 1, LVK_FORMAT_GRAY, d_frame, step, rows, cols, timestamp, d_out, out_step, out_rows, produced, out_timestamp, released, emitted);
+}
+
+// lvk_hip_stab_push for FOUR-channel frames (VideoFrame::BGRA / RGBA; BGRX is a BGRA frame): the tracker reads cvtColor(..2GRAY) of the colour bytes (pixel
+// stride 4, channel -1 for BGRA, -2 for RGBA) and the delayed frame leaves through the four-channel remap (remap_c4.hip) with background[0..3].
+int lvk_hip_stab_push_c4(lvk_hip_stab* st, const void* d_frame, int step, int rows, int cols, uint64_t timestamp, int format,
+                         void* d_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, const void** released, lvk_frame_info* emitted)
+{
+    if (!st) return LVK_HIP_ERR_ARG;
     if (produced) *produced = 0;
     if (released) *released = nullptr;
-    // (the queue's owner and format class are checked before queue_kind / pool_frames are written: a refused push leaves everything as it was)
-    int rc = lvk_stab_check_gray(st, st->gray_host_entry_now, rows, cols, timestamp, d_out, out_step, out_rows, nullptr, nullptr);
-    if (rc != LVK_HIP_OK) return rc;
-    if (st->queue.empty()) st->queue_kind = 0;
-    st->queue_kind = 1;
-    st->pool_frames = false;
-    rc = st->mark_caller_work();
-    if (rc != LVK_HIP_OK) return rc;
-    rc = lvk_stab_push_impl(st, d_frame, step, rows, cols, timestamp, LVK_FORMAT_GRAY, d_frame, step, 1, d_out, out_step, out_rows, produced, out_timestamp, released, nullptr,
-                            emitted, true);
-    if (released && !*released && !st->orphaned.empty()) { *released = st->orphaned.front(); st->orphaned.pop_front(); }
-    st->trace.mark(HostTrace::EXIT);
-    st->last_push_end = std::chrono::steady_clock::now();
-    return rc;
+    if (format != LVK_FORMAT_BGRA && format != LVK_FORMAT_RGBA)
+        return st->fail(LVK_HIP_ERR_ARG, "lvk_hip_stab_push_c4: format is LVK_FORMAT_BGRA or LVK_FORMAT_RGBA (three-channel frames go through lvk_hip_stab_push); nothing was queued");
+    return lvk_stab_push_plain(st, 4, format, d_frame, step, rows, cols, timestamp, d_out, out_step, out_rows, produced, out_timestamp, released, emitted);
 }
 
 // The OBS asynchronous path in one call: I4XXIngest / NV12Ingest::to_ocl -> StabilizationFilter::filter -> ::to_obs

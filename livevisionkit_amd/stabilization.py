@@ -164,7 +164,8 @@ class StabilizationFilter:
         `frame` is borrowed (not copied) until it has been emitted; do not modify it in the meantime.  The output has the size of the
         DELAYED frame (a stream whose frame size changes emits the queued frames at their own size): `out`, when given, must hold it
         (next_output()), and the returned tensor is its top-left rows x cols view; self.last_format = that frame's format.
-        A [rows, cols] tensor is a one-channel (GRAY) frame: it goes through lvk_hip_stab_push_gray and the output is [rows, cols] too."""
+        A [rows, cols] tensor is a one-channel (GRAY) frame: it goes through lvk_hip_stab_push_gray and the output is [rows, cols] too.
+        A [rows, cols, 4] tensor with fmt = FORMAT_BGRA or FORMAT_RGBA is a four-channel frame: lvk_hip_stab_push_c4, output [rows, cols, 4]."""
         import torch
         if profile:
             self.ctx.sync()
@@ -172,14 +173,18 @@ class StabilizationFilter:
         gray = frame.dim() == 2                                  # a [rows, cols] tensor is a one-channel (GRAY) frame: lvk_hip_stab_push_gray
         if gray:
             fmt = FORMAT_GRAY
+        c4 = frame.dim() == 3 and frame.shape[2] == 4 and fmt in (FORMAT_BGRA, FORMAT_RGBA)      # a four-channel frame: lvk_hip_stab_push_c4
         if out is None:
             due = self.next_output(frame.shape[0], frame.shape[1], fmt)
-            out = torch.empty((due[0], due[1]) if gray else (due[0], due[1], 3), dtype=torch.uint8, device=frame.device) if due else None
+            out = torch.empty((due[0], due[1]) if gray else (due[0], due[1], 4 if c4 else 3), dtype=torch.uint8, device=frame.device) if due else None
         produced = _c.c_int(0); ots = _c.c_uint64(0); released = _c.c_void_p(); info = FrameInfo()
         optr, ostep, orows = (out.data_ptr(), out.stride(0), out.shape[0]) if out is not None else (None, 0, 0)
         if gray:
             rc = self.lib.lvk_hip_stab_push_gray(self.handle, frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1], int(timestamp),
                                                  optr, ostep, orows, _c.byref(produced), _c.byref(ots), _c.byref(released), _c.byref(info))
+        elif c4:
+            rc = self.lib.lvk_hip_stab_push_c4(self.handle, frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1], int(timestamp), fmt,
+                                               optr, ostep, orows, _c.byref(produced), _c.byref(ots), _c.byref(released), _c.byref(info))
         else:
             rc = self.lib.lvk_hip_stab_push(self.handle, frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1],
                                             int(timestamp), fmt, optr, ostep, orows,
@@ -374,6 +379,38 @@ class StabilizationFilter:
         self.last_format = info.format
         return out[:info.rows, :info.cols], ots.value
 
+    # ---- host-resident four-channel frames (lvk_hip_stab_push_c4_host)
+    def host_plane_c4(self, rows, cols, pitch_extra=0):
+        """One pinned [rows, cols, 4] uint8 plane (a numpy view of a lvk_hip_host_malloc block), every row `pitch_extra` bytes (a multiple of 4) longer
+        than its pixels."""
+        import numpy as np
+        step = 4 * cols + pitch_extra
+        p = _c.c_void_p()
+        self.ctx._check(self.lib.lvk_hip_host_malloc(self.ctx.handle, rows * step, _c.byref(p)))
+        self._host_blocks = getattr(self, "_host_blocks", []); self._host_blocks.append(p)
+        block = np.ctypeslib.as_array((_c.c_uint8 * (rows * step)).from_address(p.value))
+        return np.lib.stride_tricks.as_strided(block, (rows, cols, 4), (step, 4, 1))
+
+    def apply_c4_host(self, plane, timestamp=0, out=None, fmt=FORMAT_BGRA):
+        """lvk_hip_stab_push_c4_host: a four-channel frame in a pinned host plane in (numpy uint8 [rows, cols, 4], host_plane_c4), the emitted frame -- the
+        DELAYED one, at its own size (next_output()) -- written into the pinned plane `out` (complete after Context.sync()).  Returns (the top-left view of
+        `out` that holds the frame, its timestamp) or (None, None) while the delay builds."""
+        t0 = time.perf_counter()
+        rows, cols = plane.shape[:2]
+        if out is None:
+            due = self.next_output(rows, cols, fmt)
+            out = self.host_plane_c4(due[0], due[1]) if due else None
+        produced = _c.c_int(0); ots = _c.c_uint64(0); info = FrameInfo()
+        optr, ostep, orows = (out.ctypes.data, out.strides[0], out.shape[0]) if out is not None else (None, 0, 0)
+        rc = self.lib.lvk_hip_stab_push_c4_host(self.handle, plane.ctypes.data, plane.strides[0], rows, cols, int(timestamp), int(fmt), optr, ostep, orows,
+                                                _c.byref(produced), _c.byref(ots), _c.byref(info))
+        self.ctx._check(rc)
+        self._timer._add(time.perf_counter() - t0)
+        if not produced.value:
+            return None, None
+        self.last_format = info.format
+        return out[:info.rows, :info.cols], ots.value
+
     # ---- host-resident frames of any OBS video format (lvk_hip_stab_push_obs_host)
     @staticmethod
     def obs_plane_shapes(fmt, rows, cols):
@@ -496,6 +533,10 @@ class StabilizationFilter:
     def set_overlap(self, enable=True):
         """Run the output remap on a second stream, overlapping the next frame's tracking (output valid after ctx.sync())."""
         self.ctx._check(self.lib.lvk_hip_stab_set_overlap(self.handle, 1 if enable else 0))
+
+    def set_background_alpha(self, alpha):
+        """lvk_hip_stab_set_background_alpha: background_colour[3], the fourth background byte of four-channel (BGRA / RGBA) frames (0 when never set)."""
+        self.ctx._check(self.lib.lvk_hip_stab_set_background_alpha(self.handle, int(alpha)))
 
     def set_remap_precision(self, precision):
         """REMAP_EXACT (default) or REMAP_1LSB for this filter's output remap, from the next emitted frame on: nothing restarts, the queue and the
