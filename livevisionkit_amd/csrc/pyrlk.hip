@@ -69,6 +69,45 @@ __device__ __forceinline__ void wave_sums(long long (&v)[K])
     }
 }
 
+// Two totals from two int32 partials per lane, for the Newton iteration's mismatch sums when the window is a compile-time constant of at
+// most 128 pixels (LkWalk<WIN>::ROW32).  A lane then holds at most 2 products diff * Ix with |diff| <= 8160 and |Ix| <= 4080:
+// |product| <= 8160 * 4080 = 3.33e7, a lane's partial < 6.7e7, and a 16-lane row's total < 2 * 16 * 8160 * 4080 = 1.07e9 < 2^31.  The
+// four row_shr steps are therefore exact in 32 bits; the total of the four rows needs 34 bits, so each row total is split like the
+// 64-bit form's partials and only the two cross-row steps run on both halves.  Integer sums: the same totals as wave_sums<2>, bit for bit.
+__device__ __forceinline__ int row_sum_i32(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);      // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);      // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);      // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);      // row_shr:8
+    return v;                                                           // lane 15 of each row: the row's total
+}
+
+__device__ __forceinline__ int cross_row_sum_i32(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 -> rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+__device__ __forceinline__ void wave_sums_row32(int a, int b, long long (&v)[2])
+{
+    const int ra = row_sum_i32(a), rb = row_sum_i32(b);
+    v[0] = (long long)cross_row_sum_i32(ra >> 16) * 65536 + (long long)cross_row_sum_i32(ra & 0xffff);
+    v[1] = (long long)cross_row_sum_i32(rb >> 16) * 65536 + (long long)cross_row_sum_i32(rb & 0xffff);
+}
+
+// The walk over a compile-time window: pixel p = lane + 64 r of trip r.  ROW32: the window's trips can be held in registers and their
+// row partials fit 32 bits (wave_sums_row32); otherwise (WIN = 0: the window of the arguments, or a larger constant) the iteration walks
+// the window with the 64-bit sums.
+template <int WIN>
+struct LkWalk
+{
+    static constexpr int TRIPS = WIN > 0 ? (WIN * WIN + 63) / 64 : 1;
+    static constexpr bool ROW32 = WIN > 0 && WIN * WIN <= 128;
+    static_assert(!ROW32 || (long long)TRIPS * 16 * 8160 * 4080 < (1ll << 31), "a DPP row's partial of diff * Ix must fit int32");
+};
+
 __device__ __forceinline__ void bilinear_weights(float a, float b, int& w00, int& w01, int& w10, int& w11)
 {
     w00 = (int)__builtin_rintf((1.f - a) * (1.f - b) * 16384.0f);
@@ -384,6 +423,19 @@ void k_pyrlk(PyrArgs prev, PyrArgs next, const float2* __restrict__ prev_pts, fl
     // ---- phase B: coarse to fine
     float outx = 0.f, outy = 0.f;
     bool ok = true;                                                           // status (initialised to 1 by calc())
+    // this lane's pixels of the window walk as offsets into the next-frame window (pitch jw): the same for every level and iteration.
+    // A lane without a pixel in a trip re-reads its first pixel against zero gradients (below) and so contributes exactly 0.
+    constexpr int TRIPS = LkWalk<WIN>::TRIPS;
+    int joff[TRIPS];
+    if constexpr (LkWalk<WIN>::ROW32)
+    {
+#pragma unroll
+        for (int r = 0; r < TRIPS; r++)
+        {
+            const int p = lane + 64 * r;
+            joff[r] = p < area ? (p / WIN) * jw + p % WIN : py0 * jw + px0;
+        }
+    }
     for (int level = top; level >= 0; level--)
     {
         const PyrLevel J = next.lv[level];
@@ -406,6 +458,19 @@ void k_pyrlk(PyrArgs prev, PyrArgs next, const float2* __restrict__ prev_pts, fl
         int jx0 = st.jx0, jy0 = st.jy0;
         nx -= halfx; ny -= halfy;
         float pdx = 0.f, pdy = 0.f;
+        // the level's patch samples of this lane: written by phase A, not by the re-staging below (which touches jtile alone)
+        int Ip[TRIPS], Ixp[TRIPS], Iyp[TRIPS];
+        if constexpr (LkWalk<WIN>::ROW32)
+        {
+#pragma unroll
+            for (int r = 0; r < TRIPS; r++)
+            {
+                const bool in = lane + 64 * r < area;
+                const int p = in ? lane + 64 * r : lane;                   // (one unconditional read per patch and trip)
+                const int iv = Iw[p], ixv = Ixw[p], iyv = Iyw[p];
+                Ip[r] = in ? iv : 0; Ixp[r] = in ? ixv : 0; Iyp[r] = in ? iyv : 0;
+            }
+        }
         for (int j = 0; j < max_count; j++)
         {
             const int inx = (int)__builtin_floorf(nx), iny = (int)__builtin_floorf(ny);
@@ -427,15 +492,31 @@ void k_pyrlk(PyrArgs prev, PyrArgs next, const float2* __restrict__ prev_pts, fl
             }
             const uint8_t* jt = jtile + (iny - jy0) * jw + (inx - jx0);
             long long sb[2] = {0, 0};
-            for (int p = lane, y = py0, x = px0; p < area; p += 64)
+            if constexpr (LkWalk<WIN>::ROW32)
             {
-                const int i00 = y * jw + x, i01 = i00 + 1, i10 = i00 + jw, i11 = i10 + 1;
-                const int diff = descale(__mul24(jt[i00], w00) + __mul24(jt[i01], w01) + __mul24(jt[i10], w10) + __mul24(jt[i11], w11), 14 - 5) - Iw[p];
-                sb[0] += (long long)__mul24(diff, Ixw[p]);              // |diff| <= 8160, |Ix| <= 4080
-                sb[1] += (long long)__mul24(diff, Iyw[p]);
-                y += pdy_; x += pdx_; if (x >= win_w) { x -= win_w; y++; }
+                int s0 = 0, s1 = 0;
+#pragma unroll
+                for (int r = 0; r < TRIPS; r++)
+                {
+                    const int i00 = joff[r], i01 = i00 + 1, i10 = i00 + jw, i11 = i10 + 1;
+                    const int diff = descale(__mul24(jt[i00], w00) + __mul24(jt[i01], w01) + __mul24(jt[i10], w10) + __mul24(jt[i11], w11), 14 - 5) - Ip[r];
+                    s0 += __mul24(diff, Ixp[r]);                        // |diff| <= 8160, |Ix| <= 4080
+                    s1 += __mul24(diff, Iyp[r]);
+                }
+                wave_sums_row32(s0, s1, sb);
             }
-            wave_sums<2>(sb);
+            else
+            {
+                for (int p = lane, y = py0, x = px0; p < area; p += 64)
+                {
+                    const int i00 = y * jw + x, i01 = i00 + 1, i10 = i00 + jw, i11 = i10 + 1;
+                    const int diff = descale(__mul24(jt[i00], w00) + __mul24(jt[i01], w01) + __mul24(jt[i10], w10) + __mul24(jt[i11], w11), 14 - 5) - Iw[p];
+                    sb[0] += (long long)__mul24(diff, Ixw[p]);          // |diff| <= 8160, |Ix| <= 4080
+                    sb[1] += (long long)__mul24(diff, Iyw[p]);
+                    y += pdy_; x += pdx_; if (x >= win_w) { x -= win_w; y++; }
+                }
+                wave_sums<2>(sb);
+            }
             const float b1 = (float)(double)sb[0] * FLT_SCALE, b2 = (float)(double)sb[1] * FLT_SCALE;
             const float dx = (A12 * b2 - A22 * b1) * D;
             const float dy = (A12 * b1 - A11 * b2) * D;
