@@ -150,106 +150,74 @@ class Context:
             mp, m.shape[0], m.shape[1], bgp, 1 if yuv else 0))
         return out
 
-    # ---- one-channel (GRAY) frames: channel 0 of the non-YUV EASU program on (g, c, c); src / out: torch uint8 [rows, cols] -------------
-    def _gray_out(self, src, out, shape=None):
+    # ---- one-channel (GRAY) and four-channel (BGRA / RGBA) frames: what their methods share; sfx = "_gray" / "_c4", the suffix of the C entries ----------
+    def _px_out(self, sfx, src, out, shape=None):
         import torch
-        if src.dim() != 2:
+        if sfx == "_gray" and src.dim() != 2:
             raise ValueError("a one-channel frame is a [rows, cols] uint8 tensor")
-        return out if out is not None else torch.empty(shape or tuple(src.shape), dtype=torch.uint8, device=src.device)
+        if sfx == "_c4" and (src.dim() != 3 or src.shape[2] != 4):
+            raise ValueError("a four-channel frame is a [rows, cols, 4] uint8 tensor")
+        return out if out is not None else torch.empty(tuple(shape or src.shape[:2]) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
 
+    def _px_call(self, name, sfx, src, out, bg, mid, tail=(), shape=None):
+        """lvk_hip_<name><sfx>(ctx, the src plane, the out plane, *mid, the background, *tail); out: allocated here when None (shape: not src's)."""
+        out = self._px_out(sfx, src, out, shape)
+        bga, bgp = (None, int(bg)) if sfx == "_gray" else _u8x4(bg)
+        self._check(getattr(self.lib, "lvk_hip_" + name + sfx)(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
+                                                               *mid, bgp, *tail))
+        return out
+
+    def _px_homography(self, sfx, src, H, bg, out, dst_size, offset):
+        drows, dcols = dst_size if dst_size is not None else tuple(src.shape[:2])
+        Ha, Hp = _f32(np.asarray(H, dtype=np.float32).reshape(9))
+        return self._px_call("remap_homography", sfx, src, out, bg, (drows, dcols, offset[0], offset[1], Hp), shape=(drows, dcols))
+
+    def _px_mesh(self, name, sfx, src, mesh, bg, out, lens=None):
+        ma, mp = _f32(mesh)
+        tail = () if lens is None else ((ctypes.c_double * 9)(*[float(v) for v in lens]),)
+        return self._px_call(name, sfx, src, out, bg, (mp, ma.shape[0], ma.shape[1]), tail)
+
+    def _px_map(self, sfx, src, offsets, bg, out):
+        return self._px_call("remap_map", sfx, src, out, bg, (offsets.data_ptr(), offsets.stride(0) * 4))
+
+    # ---- one-channel (GRAY) frames: channel 0 of the non-YUV EASU program on (g, c, c); src / out: torch uint8 [rows, cols] -------------
     def remap_homography_gray(self, src, H, bg=0, out=None, dst_size=None, offset=(0, 0)):
         """lvk_hip_remap_homography_gray: remap_homography for a one-channel frame, one background byte."""
-        rows, cols = src.shape
-        drows, dcols = dst_size if dst_size is not None else (rows, cols)
-        out = self._gray_out(src, out, (drows, dcols))
-        Ha, Hp = _f32(np.asarray(H, dtype=np.float32).reshape(9))
-        self._check(self.lib.lvk_hip_remap_homography_gray(self.handle, src.data_ptr(), src.stride(0), rows, cols, out.data_ptr(), out.stride(0), drows, dcols,
-                                                           offset[0], offset[1], Hp, int(bg)))
-        return out
+        return self._px_homography("_gray", src, H, bg, out, dst_size, offset)
 
     def remap_mesh_gray(self, src, mesh, bg=0, out=None):
         """lvk_hip_remap_mesh_gray: remap_mesh for a one-channel frame."""
-        out = self._gray_out(src, out)
-        m = np.ascontiguousarray(mesh, dtype=np.float32)
-        ma, mp = _f32(m)
-        self._check(self.lib.lvk_hip_remap_mesh_gray(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
-                                                     mp, m.shape[0], m.shape[1], int(bg)))
-        return out
+        return self._px_mesh("remap_mesh", "_gray", src, mesh, bg, out)
 
     def remap_map_gray(self, src, offsets, bg=0, out=None):
         """lvk_hip_remap_map_gray: remap_map for a one-channel frame (offsets: torch float32 [rows, cols, 2] on the GPU, pixels)."""
-        out = self._gray_out(src, out)
-        self._check(self.lib.lvk_hip_remap_map_gray(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
-                                                    offsets.data_ptr(), offsets.stride(0) * 4, int(bg)))
-        return out
+        return self._px_map("_gray", src, offsets, bg, out)
 
     def warpmesh_apply_gray(self, src, mesh, bg=0, out=None, lens=None):
         """lvk_hip_warpmesh_apply_gray (lens = camera params: lvk_hip_warpmesh_apply_lens_gray): WarpMesh::apply on a one-channel frame."""
-        out = self._gray_out(src, out)
-        m = np.ascontiguousarray(mesh, dtype=np.float32)
-        ma, mp = _f32(m)
-        args = (self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0), mp, m.shape[0], m.shape[1], int(bg))
-        if lens is None:
-            self._check(self.lib.lvk_hip_warpmesh_apply_gray(*args))
-        else:
-            arr = (ctypes.c_double * 9)(*[float(v) for v in lens])
-            self._check(self.lib.lvk_hip_warpmesh_apply_lens_gray(*args, arr))
-        return out
+        return self._px_mesh("warpmesh_apply" if lens is None else "warpmesh_apply_lens", "_gray", src, mesh, bg, out, lens)
 
     # ---- four-channel (BGRA / RGBA) frames: the non-YUV EASU program with a fourth channel under the same weights; src / out: torch uint8
     # [rows, cols, 4], 4-byte aligned, pitches multiples of 4; bg: four bytes ------------------------------------------------------------
-    def _c4_out(self, src, out, shape=None):
-        import torch
-        if src.dim() != 3 or src.shape[2] != 4:
-            raise ValueError("a four-channel frame is a [rows, cols, 4] uint8 tensor")
-        return out if out is not None else torch.empty((shape or tuple(src.shape[:2])) + (4,), dtype=torch.uint8, device=src.device)
-
     def remap_homography_c4(self, src, H, bg=(255, 0, 255, 255), out=None, dst_size=None, offset=(0, 0)):
         """lvk_hip_remap_homography_c4: remap_homography for a four-channel frame, four background bytes."""
-        rows, cols = src.shape[:2]
-        drows, dcols = dst_size if dst_size is not None else (rows, cols)
-        out = self._c4_out(src, out, (drows, dcols))
-        Ha, Hp = _f32(np.asarray(H, dtype=np.float32).reshape(9))
-        bga, bgp = _u8x4(bg)
-        self._check(self.lib.lvk_hip_remap_homography_c4(self.handle, src.data_ptr(), src.stride(0), rows, cols, out.data_ptr(), out.stride(0), drows, dcols,
-                                                         offset[0], offset[1], Hp, bgp))
-        return out
+        return self._px_homography("_c4", src, H, bg, out, dst_size, offset)
 
     def remap_mesh_c4(self, src, mesh, bg=(255, 0, 255, 255), out=None):
         """lvk_hip_remap_mesh_c4: remap_mesh for a four-channel frame."""
-        out = self._c4_out(src, out)
-        ma, mp = _f32(mesh)
-        bga, bgp = _u8x4(bg)
-        self._check(self.lib.lvk_hip_remap_mesh_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
-                                                   mp, ma.shape[0], ma.shape[1], bgp))
-        return out
+        return self._px_mesh("remap_mesh", "_c4", src, mesh, bg, out)
 
     def remap_map_c4(self, src, offsets, bg=(255, 0, 255, 255), out=None):
         """lvk_hip_remap_map_c4: remap_map for a four-channel frame (offsets: torch float32 [rows, cols, 2] on the GPU, pixels)."""
-        out = self._c4_out(src, out)
-        bga, bgp = _u8x4(bg)
-        self._check(self.lib.lvk_hip_remap_map_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
-                                                  offsets.data_ptr(), offsets.stride(0) * 4, bgp))
-        return out
+        return self._px_map("_c4", src, offsets, bg, out)
 
     def warpmesh_apply_c4(self, src, mesh, bg=(255, 0, 255, 255), out=None):
         """lvk_hip_warpmesh_apply_c4: WarpMesh::apply on a four-channel frame."""
-        out = self._c4_out(src, out)
-        ma, mp = _f32(mesh)
-        bga, bgp = _u8x4(bg)
-        self._check(self.lib.lvk_hip_warpmesh_apply_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
-                                                       mp, ma.shape[0], ma.shape[1], bgp))
-        return out
+        return self._px_mesh("warpmesh_apply", "_c4", src, mesh, bg, out)
 
     def warpmesh_apply_lens_c4(self, src, mesh, lens, bg=(255, 0, 255, 255), out=None):
         """lvk_hip_warpmesh_apply_lens_c4: the lens pre-warp (camera params) fused into WarpMesh::apply on a four-channel frame."""
-        out = self._c4_out(src, out)
-        ma, mp = _f32(mesh)
-        bga, bgp = _u8x4(bg)
-        arr = (ctypes.c_double * 9)(*[float(v) for v in lens])
-        self._check(self.lib.lvk_hip_warpmesh_apply_lens_c4(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1], out.data_ptr(), out.stride(0),
-                                                            mp, ma.shape[0], ma.shape[1], bgp, arr))
-        return out
+        return self._px_mesh("warpmesh_apply_lens", "_c4", src, mesh, bg, out, lens)
 
     # ---- a3/a4/a7 image ops --------------------------------------------------------------------------
     def luma_area_resize(self, frame, drows, dcols, channel=0):

@@ -388,7 +388,7 @@ int lvk_launch_lens_undistort(lvk_hip_ctx* ctx, hipStream_t stream, const LensMo
 int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
                                    void* d_dst, int dst_step, const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const RemapLaunch& o);
 
-// Dense remap of one-channel (8UC1) frames (remap_gray.hip): channel 0 of the non-YUV EASU program on (g, c, c); bg = the background byte
+// Dense remap of one-channel (8UC1) frames (remap_px.hip, GrayPix): channel 0 of the non-YUV EASU program on (g, c, c); bg = the background byte
 int lvk_launch_remap_homography_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
                                      void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], uint8_t bg, const RemapLaunch& o);
 int lvk_launch_remap_mesh_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
@@ -398,7 +398,7 @@ int lvk_launch_remap_map_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step,
 int lvk_launch_warpmesh_apply_lens_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step,
                                         const float* mesh, int mesh_rows, int mesh_cols, uint8_t bg, const RemapLaunch& o);
 
-// Dense remap of four-channel (8UC4) frames (remap_c4.hip): the non-YUV EASU program with a fourth channel under the same weights; bg = the four background
+// Dense remap of four-channel (8UC4) frames (remap_px.hip, C4Pix): the non-YUV EASU program with a fourth channel under the same weights; bg = the four background
 // bytes.  Both planes 4-byte aligned with pitches that are multiples of 4.
 int lvk_launch_remap_homography_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols,
                                    void* d_dst, int dst_step, int dst_rows, int dst_cols, int off_x, int off_y, const float H[9], const uint8_t bg[4], const RemapLaunch& o);

@@ -146,8 +146,7 @@ int lvk_launch_remap_map(lvk_hip_ctx* ctx, const void* d_src, int src_step, int 
 {
     LVK_HIP_REQUIRE(ctx, remap_precision_known(o.precision));
     LVK_HIP_REQUIRE(ctx, bg != nullptr);                                                                 // Image.cpp:30-34
-    LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_src, src_step, rows, cols, 3) && remap_plane_ok(d_dst, dst_step, rows, cols, 3) && remap_plane_ok(d_map, map_step, rows, cols, 8));
-    LVK_HIP_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_map) | (uintptr_t)map_step) & 7u) == 0);
+    LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_src, src_step, rows, cols, 3) && remap_plane_ok(d_dst, dst_step, rows, cols, 3) && remap_map_ok(d_map, map_step, rows, cols));
     // (a materialised map has no lens form and no persistent grid: of `o` the stream and the precision are read)
     launch_remap(ctx, LVK_REMAP_FORMS(k_remap_map, false, true), yuv != 0, rows, cols, RemapLaunch{o.stream, o.precision}, 0, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step,
                  (const uint8_t*)d_map, map_step, pack_bg(bg));
@@ -180,14 +179,9 @@ int lvk_launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, const void* d_src, int src_
                                    void* d_dst, int dst_step,
                                    const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], int yuv, const RemapLaunch& o)
 {
-    LVK_HIP_REQUIRE(ctx, remap_mesh_ok(mesh, mesh_rows, mesh_cols));
-    if (mesh_rows == 2 && mesh_cols == 2)
-    {
-        float H[9];
-        lvkh::mesh2x2_to_homography(mesh, rows, cols, H);
-        return lvk_launch_remap_homography(ctx, d_src, src_step, rows, cols, d_dst, dst_step, rows, cols, 0, 0, H, bg, yuv, o);
-    }
-    return lvk_launch_remap_mesh(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, o);
+    return route_warpmesh(ctx, mesh, mesh_rows, mesh_cols, rows, cols,
+                          [&](const float H[9]) { return lvk_launch_remap_homography(ctx, d_src, src_step, rows, cols, d_dst, dst_step, rows, cols, 0, 0, H, bg, yuv, o); },
+                          [&] { return lvk_launch_remap_mesh(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, o); });
 }
 
 // WarpMesh::apply + I4XXIngest / NV12Ingest::to_obs in one launch: d_src packed YUV 8UC3, output planar 4:2:0 (I420: y, u, v; NV12: y, uv).
@@ -251,10 +245,9 @@ int lvk_hip_warpmesh_apply_lens(lvk_hip_ctx* ctx, const void* d_src, int src_ste
 {
     LVK_HIP_ENTRY(ctx);
     LVK_HIP_REQUIRE(ctx, lens != nullptr && rows > 1 && cols > 1);
-    LensModel m; LensArgs a;
-    const int rc = lvk_lens_model_build(*lens, rows, cols, m);
-    if (rc != LVK_HIP_OK) return ctx->fail(rc, "invalid camera profile");
-    std::memcpy(a.f, m.f, sizeof(a.f));
+    LensArgs a;
+    const int rc = lens_args_of(ctx, lens, rows, cols, a);
+    if (rc != LVK_HIP_OK) return rc;
     return lvk_launch_warpmesh_apply_lens(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, yuv, RemapLaunch{ctx->stream, ctx->remap_precision, &a});
 }
 

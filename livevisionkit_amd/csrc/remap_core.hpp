@@ -1,9 +1,9 @@
 // (remap_core.hpp: the device code and host helpers shared by remap.hip -- the packed and 4:2:0 kernels and their launchers --, remap_obs.hip -- the
-//  fused remap + egress kernels of the other OBS video formats -- and remap_gray.hip.  Everything lives in an anonymous namespace: each translation unit
+//  fused remap + egress kernels of the other OBS video formats -- and remap_px.hip -- the one- and four-channel kernels.  Everything lives in an anonymous namespace: each translation unit
 //  has its own copy.  Device side: EASU, the coordinate functors and their builders (lens_coord, with_homography_coord, LVK_WITH_MESH_COORD), the sinks, the
 //  strip walk (walk_strips) and the homography kernels' body remap_homography.  Host side, at the end: the kernel-defining macros with the table of a family's
-//  forms and the one launch (launch_remap), the grids, the argument rules, and the mesh staging protocol (with_staged_mesh).  The 2 x 2 mesh route is
-//  lvkh::mesh2x2_to_homography in host_logic.hpp.)
+//  forms and the one launch (launch_remap), the grids, the argument rules, the 2 x 2 mesh route (route_warpmesh, over lvkh::mesh2x2_to_homography in
+//  host_logic.hpp) and the mesh staging protocol (with_staged_mesh).)
 //
 // Dense frame remap for gfx950: the EASU (edge adaptive, 12-tap) resampler driven either by a 3x3
 // homography or by a warp mesh that is interpolated inside the kernel.
@@ -707,6 +707,36 @@ inline bool remap_plane_ok(const void* p, int step, int rows, int cols, int bpp)
 }
 
 inline bool remap_mesh_ok(const float* mesh, int mesh_rows, int mesh_cols) { return mesh != nullptr && mesh_rows >= 2 && mesh_cols >= 2; }   // WarpMesh::MinimumSize
+
+// a materialised offset map (MapCoord): a plane of rows x cols float2, read as aligned 8-byte loads
+inline bool remap_map_ok(const void* d_map, int map_step, int rows, int cols)
+{
+    return remap_plane_ok(d_map, map_step, rows, cols, 8) && ((reinterpret_cast<uintptr_t>(d_map) | (uintptr_t)map_step) & 7u) == 0;
+}
+
+// the camera profile of a `_lens` C entry as the kernels take it, for a rows x cols frame (lens != nullptr, rows > 1, cols > 1: the entry has checked)
+inline int lens_args_of(lvk_hip_ctx* ctx, const lvk_camera_params* lens, int rows, int cols, LensArgs& a)
+{
+    LensModel m;
+    const int rc = lvk_lens_model_build(*lens, rows, cols, m);
+    if (rc != LVK_HIP_OK) return ctx->fail(rc, "invalid camera profile");
+    std::memcpy(a.f, m.f, sizeof(a.f));
+    return LVK_HIP_OK;
+}
+
+// WarpMesh::apply of a rows x cols frame: a 2 x 2 mesh goes through the homography kernel, homography(H), anything larger through the mesh kernel, larger()
+template <class LaunchH, class LaunchM>
+inline int route_warpmesh(lvk_hip_ctx* ctx, const float* mesh, int mesh_rows, int mesh_cols, int rows, int cols, const LaunchH& homography, const LaunchM& larger)
+{
+    LVK_HIP_REQUIRE(ctx, remap_mesh_ok(mesh, mesh_rows, mesh_cols));
+    if (mesh_rows == 2 && mesh_cols == 2)
+    {
+        float H[9];
+        lvkh::mesh2x2_to_homography(mesh, rows, cols, H);
+        return homography(H);
+    }
+    return larger();
+}
 
 inline uint32_t pack_bg(const uint8_t bg[3]) { return (uint32_t)bg[0] | ((uint32_t)bg[1] << 8) | ((uint32_t)bg[2] << 16); }
 

@@ -14,7 +14,7 @@ f32 = np.float32
 BG = 77
 # 2 x 2 and 5 x 5: every pixel is border or background (the EASU interior needs 6 x 6); 63 x 65, 64 x 64, 257 x 129: the wave (64 lanes x 4 pixels), block
 # (4 rows) and strip (256 columns) edges of the launch geometry; 253 .. 257 columns: the strip width -3 .. +1 (a misaligned row is shifted by up to 3 bytes)
-SIZES = [(2, 2), (5, 5), (6, 7), (63, 65), (64, 64), (257, 129), (129, 257), (9, 253), (9, 255), (9, 256)]
+SIZES = [(2, 2), (5, 5), (6, 7), (63, 65), (64, 64), (257, 129), (129, 257), (9, 253), (9, 255), (9, 256), (9, 257)]
 LENS = lambda r, c: (0.8 * c, 0.8 * c, c / 2, r / 2, -0.12, 0.03, 0, 0, 0)
 
 

@@ -87,13 +87,13 @@ def test_one_lsb_twins_issue_seven_percent_fewer_valu_within_the_register_budget
 
 def test_every_covered_kernel_has_a_twin_and_the_uncovered_ones_have_none():
     names = set()
-    for unit in ("remap", "remap_obs", "remap_gray"):
+    for unit in ("remap", "remap_obs", "remap_px"):
         names |= {re.search(r"\d+(k_\w+?)I", k).group(1) for k in assemble(unit)[1] if re.search(r"\d+(k_\w+?)I", k)}
     exact = {n for n in names if not n.endswith("_r1")}
     for n in exact:
-        covered = n.startswith("k_remap_") and "gray" not in n
+        covered = n.startswith("k_remap_") and not n.endswith("_px")        # `_px`: the one- and four-channel kernels (remap_px.hip)
         assert ((n + "_r1") in names) == covered, n
-    assert "k_easu_scale" in exact and "k_remap_homography_planes" in exact and any("gray" in n for n in exact)
+    assert "k_easu_scale" in exact and "k_remap_homography_planes" in exact and {"k_remap_homography_px", "k_remap_mesh_px", "k_remap_map_px"} <= exact
 
 
 def test_boundary_carries_the_four_symbols():
