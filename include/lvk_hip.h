@@ -684,18 +684,21 @@ int  lvk_hip_mesh_solver_solve(lvk_hip_mesh_solver* solver, const float* tracked
  * VideoFrame::viewAsFormat(GRAY) for YUV frames (= channel 0, Data/VideoFrame.cpp:260) fused with
  * cv::resize(gray, detection_resolution, INTER_AREA) (Vision/FrameTracker.cpp:117).
  * pix_stride = bytes per source pixel (3 packed 8UC3, 1 planar); d_dst is 8UC1 drows x dcols.  Any pair of sizes: integer and fractional
- * reductions, and (a frame smaller than the detection resolution) cv::resize's bilinear emulation of INTER_AREA towards a larger image. */
+ * reductions, and (a frame smaller than the detection resolution) cv::resize's bilinear emulation of INTER_AREA towards a larger image.
+ * LVK_HIP_ERR_ARG, nothing written, for a pitch shorter than its row (src_step < scols * pix_stride, dst_step < dcols), like the remap entries. */
 int lvk_hip_luma_area_resize(lvk_hip_ctx* ctx, const void* d_src, int src_step, int pix_stride, int channel,
                              int srows, int scols, void* d_dst, int dst_step, int drows, int dcols);
 
 /* ---- a7 (pyramid): cv::pyrDown and the Scharr derivative image that cv::SparsePyrLKOpticalFlow::calc builds
  * internally (Vision/FrameTracker.cpp:140-146).  d_dst of pyr_down is ((cols+1)/2) x ((rows+1)/2) 8UC1;
- * d_dst of scharr is rows x cols x (Ix, Iy) int16, tightly packed. */
+ * d_dst of scharr is rows x cols x (Ix, Iy) int16, tightly packed.  LVK_HIP_ERR_ARG, nothing written, for a pitch shorter than its row
+ * (src_step < cols; pyr_down: dst_step < (cols + 1) / 2), like the remap entries. */
 int lvk_hip_pyr_down(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step);
 int lvk_hip_scharr(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst);
 
 /* The whole optical-flow pyramid of buildOpticalFlowPyramid (levels until one would be <= the window) plus every
- * level's Scharr image, returned to the host tightly packed level after level.  Returns the level count.  Synchronous. */
+ * level's Scharr image, returned to the host tightly packed level after level.  Returns the level count.  Synchronous.
+ * LVK_HIP_ERR_ARG, nothing written, for step < cols, like the remap entries. */
 int lvk_hip_build_pyramid(lvk_hip_ctx* ctx, const void* d_img, int step, int rows, int cols, int max_level, int win_w, int win_h,
                           uint8_t* levels, int16_t* derivs, int* level_rows, int* level_cols);
 
@@ -703,7 +706,7 @@ int lvk_hip_build_pyramid(lvk_hip_ctx* ctx, const void* d_img, int step, int row
  * cv::FastFeatureDetector(threshold, true, TYPE_9_16)->detect(frame(region)) (Vision/FeatureDetector.cpp:130-134).
  * regions = nregions x {x, y, w, h, threshold, active} ints; out = nregions x cap keypoints packed as
  * x | y << 12 | score << 24 (region-local, row-major like the CPU detector); counts = nregions totals.
- * Synchronous (returns after the results are on the host). */
+ * Synchronous (returns after the results are on the host).  LVK_HIP_ERR_ARG, nothing written, for step < cols, like the remap entries. */
 int lvk_hip_fast_detect(lvk_hip_ctx* ctx, const void* d_img, int step, int rows, int cols,
                         const int* regions, int nregions, uint32_t* out, int cap, int* counts);
 
@@ -793,6 +796,23 @@ int lvk_hip_fsr_easu_const(int rw, int rh, int W, int H, int ow, int oh, float c
 /* The kernel path lvk_hip_fsr_easu takes for a rw x rh region scaled to out_rows x out_cols: 0 = staged (the tile's source footprint in
  * LDS), 1 = direct (taps read from the frame; downscales whose footprint does not fit).  Needs no device.  LVK_HIP_ERR_ARG for a size <= 0. */
 int lvk_hip_fsr_easu_path(int rw, int rh, int out_rows, int out_cols);
+
+/* The kernel form lvk_hip_luma_area_resize (and the stabilizer's tracking-frame downscale, the same launcher) runs for these arguments: one
+ * value per form, chosen by the exactness of the scale, the pixel stride, the channel, the tap count per axis and the alignment of the
+ * source base and pitch.  FAST_DW_<sx>x<sy>_<source>: the dword-load kernels for 4-byte aligned planes (C3 = packed three-byte pixels,
+ * channel 0 / BGR -> gray / RGB -> gray; C1 = planar); FAST: any other integer scale; TILE_<n> (planar, LDS window) and TAPS_<n> (one channel
+ * of packed pixels): fractional scales with up to n taps per axis; GENERAL: the tap loops; ENLARGE: a destination larger on either axis.
+ * Launches nothing (a fractional scale stages its tap tables in the context, as the resize itself would).  Returns the form, or
+ * LVK_HIP_ERR_* for arguments the resize refuses. */
+enum
+{
+    LVK_AREA_PATH_FAST_DW_8x8_C3_BGR = 0, LVK_AREA_PATH_FAST_DW_8x8_C3_RGB = 1, LVK_AREA_PATH_FAST_DW_4x4_C3_BGR = 2, LVK_AREA_PATH_FAST_DW_4x4_C3_RGB = 3,
+    LVK_AREA_PATH_FAST_DW_8x8_C3 = 4, LVK_AREA_PATH_FAST_DW_4x4_C3 = 5, LVK_AREA_PATH_FAST_DW_8x8_C1 = 6, LVK_AREA_PATH_FAST_DW_4x4_C1 = 7,
+    LVK_AREA_PATH_FAST = 8, LVK_AREA_PATH_TILE_4 = 9, LVK_AREA_PATH_TILE_8 = 10, LVK_AREA_PATH_TAPS_4 = 11, LVK_AREA_PATH_TAPS_8 = 12,
+    LVK_AREA_PATH_GENERAL = 13, LVK_AREA_PATH_ENLARGE = 14, LVK_AREA_PATH_COUNT = 15
+};
+int lvk_hip_area_resize_path(lvk_hip_ctx* ctx, const void* d_src, int src_step, int pix_stride, int channel,
+                             int srows, int scols, int drows, int dcols);
 
 #ifdef __cplusplus
 }

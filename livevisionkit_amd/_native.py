@@ -160,6 +160,7 @@ _SIG = {
                                         _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "lvk_hip_fsr_easu_const": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)]),
     "lvk_hip_fsr_easu_path": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_area_resize_path": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
 }
 
 _lib = None

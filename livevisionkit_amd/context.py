@@ -220,25 +220,37 @@ class Context:
         return self._px_mesh("warpmesh_apply_lens", "_c4", src, mesh, bg, out, lens)
 
     # ---- a3/a4/a7 image ops --------------------------------------------------------------------------
-    def luma_area_resize(self, frame, drows, dcols, channel=0):
-        """frame: torch uint8 [rows, cols, 3] (packed) or [rows, cols] (planar) -> [drows, dcols] uint8."""
+    def luma_area_resize(self, frame, drows, dcols, channel=0, out=None):
+        """frame: torch uint8 [rows, cols, pix] (packed) or [rows, cols] (planar), any base and pitch -> [drows, dcols] uint8 (out: written in place,
+        any pitch)."""
         import torch
         pix = frame.shape[2] if frame.dim() == 3 else 1
-        out = torch.empty((drows, dcols), dtype=torch.uint8, device=frame.device)
+        if out is None:
+            out = torch.empty((drows, dcols), dtype=torch.uint8, device=frame.device)
         self._check(self.lib.lvk_hip_luma_area_resize(self.handle, frame.data_ptr(), frame.stride(0), pix, channel,
                                                       frame.shape[0], frame.shape[1], out.data_ptr(), out.stride(0), drows, dcols))
         return out
 
-    def pyr_down(self, img):
+    def area_resize_path(self, frame, drows, dcols, channel=0):
+        """lvk_hip_area_resize_path: the LVK_AREA_PATH_* form luma_area_resize runs for this frame (its base and pitch count) and these sizes."""
+        pix = frame.shape[2] if frame.dim() == 3 else 1
+        path = self.lib.lvk_hip_area_resize_path(self.handle, frame.data_ptr(), frame.stride(0), pix, channel, frame.shape[0], frame.shape[1], drows, dcols)
+        self._check(min(path, 0))
+        return path
+
+    def pyr_down(self, img, out=None):
         import torch
-        out = torch.empty(((img.shape[0] + 1) // 2, (img.shape[1] + 1) // 2), dtype=torch.uint8, device=img.device)
+        if out is None:
+            out = torch.empty(((img.shape[0] + 1) // 2, (img.shape[1] + 1) // 2), dtype=torch.uint8, device=img.device)
         self._check(self.lib.lvk_hip_pyr_down(self.handle, img.data_ptr(), img.stride(0), img.shape[0], img.shape[1],
                                               out.data_ptr(), out.stride(0)))
         return out
 
-    def scharr(self, img):
+    def scharr(self, img, out=None):
+        """out: a contiguous int16 [rows, cols, 2] tensor (the derivative image is tightly packed)."""
         import torch
-        out = torch.empty((img.shape[0], img.shape[1], 2), dtype=torch.int16, device=img.device)
+        if out is None:
+            out = torch.empty((img.shape[0], img.shape[1], 2), dtype=torch.int16, device=img.device)
         self._check(self.lib.lvk_hip_scharr(self.handle, img.data_ptr(), img.stride(0), img.shape[0], img.shape[1], out.data_ptr()))
         return out
 

@@ -404,7 +404,7 @@ int lvk_hip_fast_detect(lvk_hip_ctx* ctx, const void* d_img, int step, int rows,
                         const int* regions, int nregions, uint32_t* out, int cap, int* counts)
 {
     LVK_HIP_ENTRY(ctx);
-    LVK_HIP_REQUIRE(ctx, regions && out && counts && nregions > 0 && cap > 0);
+    LVK_HIP_REQUIRE(ctx, regions && out && counts && nregions > 0 && cap > 0 && rows > 0 && cols > 0 && step >= cols);
     std::vector<FastRegion> rg((size_t)nregions);
     int max_rw = 1, max_rh = 1;
     for (int i = 0; i < nregions; i++)

@@ -510,72 +510,84 @@ int lvk_get_areatab(lvk_hip_ctx* ctx, int ssize, int dsize, const int2** d_range
     return LVK_HIP_OK;
 }
 
+// The one place where the downscale's kernel form is chosen (lvk_hip.h: LVK_AREA_PATH_*): the launcher below switches on the result, the
+// query entry returns it.  A fractional scale needs its tap tables for the choice (tap count, window span); they come back in `t`.
+struct AreaTabs { const int2 *xr = nullptr, *yr = nullptr; const AreaTabEntry *xt = nullptr, *yt = nullptr; };
+
+static int lvk_area_resize_path(lvk_hip_ctx* ctx, const void* d_src, int src_step, int pix_stride, int channel,
+                                int srows, int scols, int drows, int dcols, AreaTabs* t)
+{
+    LVK_HIP_REQUIRE(ctx, d_src && srows > 0 && scols > 0 && drows > 0 && dcols > 0);
+    LVK_HIP_REQUIRE(ctx, pix_stride >= 1 && channel >= -2 && channel < pix_stride && (channel >= 0 || pix_stride >= 3));
+    LVK_HIP_REQUIRE(ctx, (long)src_step >= (long)scols * pix_stride);
+    // a frame smaller than the detection resolution on either axis (FrameTracker.cpp:117 resizes whatever it is given)
+    if (drows > srows || dcols > scols) return LVK_AREA_PATH_ENLARGE;
+    const int isx = scols / dcols, isy = srows / drows;
+    if (scols % dcols == 0 && srows % drows == 0)
+    {
+        const bool aligned = (reinterpret_cast<uintptr_t>(d_src) & 3u) == 0 && (src_step & 3) == 0;
+        const bool s8 = isx == 8 && isy == 8, s4 = isx == 4 && isy == 4;
+        if (aligned && (s8 || s4))
+        {
+            if (pix_stride == 3 && channel == -1) return s8 ? LVK_AREA_PATH_FAST_DW_8x8_C3_BGR : LVK_AREA_PATH_FAST_DW_4x4_C3_BGR;
+            if (pix_stride == 3 && channel == -2) return s8 ? LVK_AREA_PATH_FAST_DW_8x8_C3_RGB : LVK_AREA_PATH_FAST_DW_4x4_C3_RGB;
+            if (pix_stride == 3 && channel == 0) return s8 ? LVK_AREA_PATH_FAST_DW_8x8_C3 : LVK_AREA_PATH_FAST_DW_4x4_C3;
+            if (pix_stride == 1 && channel == 0) return s8 ? LVK_AREA_PATH_FAST_DW_8x8_C1 : LVK_AREA_PATH_FAST_DW_4x4_C1;
+        }
+        return LVK_AREA_PATH_FAST;
+    }
+    int rc, xtaps = 0, ytaps = 0, xspan = 0, yspan = 0, unused = 0;
+    if ((rc = lvk_get_areatab(ctx, scols, dcols, &t->xr, &t->xt, &xtaps, &xspan, &unused)) != LVK_HIP_OK) return rc;
+    if ((rc = lvk_get_areatab(ctx, srows, drows, &t->yr, &t->yt, &ytaps, &unused, &yspan)) != LVK_HIP_OK) return rc;
+    const int taps = std::max(xtaps, ytaps);
+    if (pix_stride == 1 && channel == 0 && taps >= 1 && taps <= 8 && xspan + 6 <= AT_W && yspan <= AT_H)
+        return taps <= 4 ? LVK_AREA_PATH_TILE_4 : LVK_AREA_PATH_TILE_8;
+    if (channel >= 0 && taps >= 1 && taps <= 8) return taps <= 4 ? LVK_AREA_PATH_TAPS_4 : LVK_AREA_PATH_TAPS_8;
+    return LVK_AREA_PATH_GENERAL;
+}
+
 int lvk_launch_luma_area_resize(lvk_hip_ctx* ctx, const void* d_src, int src_step, int pix_stride, int channel,
                                 int srows, int scols, void* d_dst, int dst_step, int drows, int dcols)
 {
-    LVK_HIP_REQUIRE(ctx, d_src && d_dst && srows > 0 && scols > 0 && drows > 0 && dcols > 0);
-    LVK_HIP_REQUIRE(ctx, pix_stride >= 1 && channel >= -2 && channel < pix_stride && (channel >= 0 || pix_stride >= 3));
+    LVK_HIP_REQUIRE(ctx, d_dst && dcols > 0 && dst_step >= dcols);
+    AreaTabs t;
+    const int path = lvk_area_resize_path(ctx, d_src, src_step, pix_stride, channel, srows, scols, drows, dcols, &t);
+    if (path < 0) return path;
     const dim3 block(64, 4), grid((dcols + 63) / 64, (drows + 3) / 4);
-    if (drows > srows || dcols > scols)
+    const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
+#define LVK_AREA_DW(SX, SY, PIX, MODE) hipLaunchKernelGGL((k_area_fast_dw<SX, SY, PIX, MODE>), grid, block, 0, ctx->stream, src, src_step, dst, dst_step, drows, dcols)
+#define LVK_AREA_TABS(kernel, ...) hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, src, src_step, __VA_ARGS__, dst, dst_step, drows, dcols, t.xr, t.xt, t.yr, t.yt)
+    switch (path)
     {
-        // a frame smaller than the detection resolution on either axis (FrameTracker.cpp:117 resizes whatever it is given)
+    case LVK_AREA_PATH_FAST_DW_8x8_C3_BGR: LVK_AREA_DW(8, 8, 3, 1); break;
+    case LVK_AREA_PATH_FAST_DW_8x8_C3_RGB: LVK_AREA_DW(8, 8, 3, 2); break;
+    case LVK_AREA_PATH_FAST_DW_4x4_C3_BGR: LVK_AREA_DW(4, 4, 3, 1); break;
+    case LVK_AREA_PATH_FAST_DW_4x4_C3_RGB: LVK_AREA_DW(4, 4, 3, 2); break;
+    case LVK_AREA_PATH_FAST_DW_8x8_C3:     LVK_AREA_DW(8, 8, 3, 0); break;
+    case LVK_AREA_PATH_FAST_DW_4x4_C3:     LVK_AREA_DW(4, 4, 3, 0); break;
+    case LVK_AREA_PATH_FAST_DW_8x8_C1:     LVK_AREA_DW(8, 8, 1, 0); break;
+    case LVK_AREA_PATH_FAST_DW_4x4_C1:     LVK_AREA_DW(4, 4, 1, 0); break;
+    case LVK_AREA_PATH_FAST:
+        hipLaunchKernelGGL(k_area_fast, grid, block, 0, ctx->stream, src, src_step, pix_stride, channel, dst, dst_step, drows, dcols, scols / dcols, srows / drows);
+        break;
+    case LVK_AREA_PATH_TILE_4:  LVK_AREA_TABS(k_area_general_tile<4>, scols); break;
+    case LVK_AREA_PATH_TILE_8:  LVK_AREA_TABS(k_area_general_tile<8>, scols); break;
+    case LVK_AREA_PATH_TAPS_4:  LVK_AREA_TABS(k_area_general_taps<4>, pix_stride, channel); break;
+    case LVK_AREA_PATH_TAPS_8:  LVK_AREA_TABS(k_area_general_taps<8>, pix_stride, channel); break;
+    case LVK_AREA_PATH_GENERAL: LVK_AREA_TABS(k_area_general, pix_stride, channel); break;
+    case LVK_AREA_PATH_ENLARGE:
+    {
         const int4 *xt, *yt;
         int rc;
         if ((rc = lvk_get_enlargetab(ctx, scols, dcols, true, &xt)) != LVK_HIP_OK) return rc;
         if ((rc = lvk_get_enlargetab(ctx, srows, drows, false, &yt)) != LVK_HIP_OK) return rc;
-        hipLaunchKernelGGL(k_area_enlarge, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, pix_stride, channel, (uint8_t*)d_dst, dst_step, drows, dcols, xt, yt);
-        LVK_HIP_CHECK(ctx, hipGetLastError());
-        return LVK_HIP_OK;
+        hipLaunchKernelGGL(k_area_enlarge, grid, block, 0, ctx->stream, src, src_step, pix_stride, channel, dst, dst_step, drows, dcols, xt, yt);
+        break;
     }
-    const int isx = scols / dcols, isy = srows / drows;
-    const bool exact = scols % dcols == 0 && srows % drows == 0;
-    const bool aligned = (reinterpret_cast<uintptr_t>(d_src) & 3u) == 0 && (src_step & 3) == 0;
-    const bool dw_ok = exact && channel == 0 && aligned;
-    const bool dw_rgb = exact && channel < 0 && aligned && pix_stride == 3;
-    if (dw_rgb && isx == 8 && isy == 8 && channel == -1)
-        hipLaunchKernelGGL((k_area_fast_dw<8, 8, 3, 1>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (dw_rgb && isx == 8 && isy == 8)
-        hipLaunchKernelGGL((k_area_fast_dw<8, 8, 3, 2>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (dw_rgb && isx == 4 && isy == 4 && channel == -1)
-        hipLaunchKernelGGL((k_area_fast_dw<4, 4, 3, 1>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (dw_rgb && isx == 4 && isy == 4)
-        hipLaunchKernelGGL((k_area_fast_dw<4, 4, 3, 2>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (dw_ok && isx == 8 && isy == 8 && pix_stride == 3)
-        hipLaunchKernelGGL((k_area_fast_dw<8, 8, 3>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (dw_ok && isx == 4 && isy == 4 && pix_stride == 3)
-        hipLaunchKernelGGL((k_area_fast_dw<4, 4, 3>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (dw_ok && isx == 8 && isy == 8 && pix_stride == 1)
-        hipLaunchKernelGGL((k_area_fast_dw<8, 8, 1>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (dw_ok && isx == 4 && isy == 4 && pix_stride == 1)
-        hipLaunchKernelGGL((k_area_fast_dw<4, 4, 1>), grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, (uint8_t*)d_dst, dst_step, drows, dcols);
-    else if (exact)
-    {
-        hipLaunchKernelGGL(k_area_fast, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, pix_stride, channel,
-                           (uint8_t*)d_dst, dst_step, drows, dcols, scols / dcols, srows / drows);
+    default: return ctx->fail(LVK_HIP_ERR_ARG, "no such downscale form");
     }
-    else
-    {
-        const int2 *xr, *yr; const AreaTabEntry *xt, *yt;
-        int rc;
-        int xtaps = 0, ytaps = 0, xspan = 0, yspan = 0, unused = 0;
-        if ((rc = lvk_get_areatab(ctx, scols, dcols, &xr, &xt, &xtaps, &xspan, &unused)) != LVK_HIP_OK) return rc;
-        if ((rc = lvk_get_areatab(ctx, srows, drows, &yr, &yt, &ytaps, &unused, &yspan)) != LVK_HIP_OK) return rc;
-        const int taps = std::max(xtaps, ytaps);
-        const bool tile_ok = pix_stride == 1 && channel == 0 && taps >= 1 && taps <= 8 && xspan + 6 <= AT_W && yspan <= AT_H;
-        if (tile_ok && taps <= 4)
-            hipLaunchKernelGGL(k_area_general_tile<4>, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, scols, (uint8_t*)d_dst, dst_step, drows, dcols, xr, xt, yr, yt);
-        else if (tile_ok)
-            hipLaunchKernelGGL(k_area_general_tile<8>, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, scols, (uint8_t*)d_dst, dst_step, drows, dcols, xr, xt, yr, yt);
-        else if (channel >= 0 && taps >= 1 && taps <= 4)
-            hipLaunchKernelGGL(k_area_general_taps<4>, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, pix_stride, channel,
-                               (uint8_t*)d_dst, dst_step, drows, dcols, xr, xt, yr, yt);
-        else if (channel >= 0 && taps >= 1 && taps <= 8)
-            hipLaunchKernelGGL(k_area_general_taps<8>, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, pix_stride, channel,
-                               (uint8_t*)d_dst, dst_step, drows, dcols, xr, xt, yr, yt);
-        else
-        hipLaunchKernelGGL(k_area_general, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, pix_stride, channel,
-                           (uint8_t*)d_dst, dst_step, drows, dcols, xr, xt, yr, yt);
-    }
+#undef LVK_AREA_DW
+#undef LVK_AREA_TABS
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
 }
@@ -584,6 +596,7 @@ int lvk_launch_pyr_down(lvk_hip_ctx* ctx, const void* d_src, int src_step, int r
 {
     LVK_HIP_REQUIRE(ctx, d_src && d_dst && rows > 0 && cols > 0);
     const int drows = (rows + 1) / 2, dcols = (cols + 1) / 2;
+    LVK_HIP_REQUIRE(ctx, src_step >= cols && dst_step >= dcols);
     const dim3 block(64, 4), grid((dcols + 63) / 64, (drows + 3) / 4);
     hipLaunchKernelGGL(k_pyr_down, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_dst, dst_step, drows, dcols);
     LVK_HIP_CHECK(ctx, hipGetLastError());
@@ -592,7 +605,7 @@ int lvk_launch_pyr_down(lvk_hip_ctx* ctx, const void* d_src, int src_step, int r
 
 int lvk_launch_scharr(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst)
 {
-    LVK_HIP_REQUIRE(ctx, d_src && d_dst && rows > 0 && cols > 0);
+    LVK_HIP_REQUIRE(ctx, d_src && d_dst && rows > 0 && cols > 0 && src_step >= cols);
     const dim3 block(64, 4), grid((cols + 63) / 64, (rows + 3) / 4);
     hipLaunchKernelGGL(k_scharr, grid, block, 0, ctx->stream, (const uint8_t*)d_src, src_step, rows, cols, (short2*)d_dst);
     LVK_HIP_CHECK(ctx, hipGetLastError());
@@ -628,6 +641,13 @@ int lvk_hip_luma_area_resize(lvk_hip_ctx* ctx, const void* d_src, int src_step, 
 {
     LVK_HIP_ENTRY(ctx);
     return lvk_launch_luma_area_resize(ctx, d_src, src_step, pix_stride, channel, srows, scols, d_dst, dst_step, drows, dcols);
+}
+
+int lvk_hip_area_resize_path(lvk_hip_ctx* ctx, const void* d_src, int src_step, int pix_stride, int channel, int srows, int scols, int drows, int dcols)
+{
+    LVK_HIP_ENTRY(ctx);
+    AreaTabs t;
+    return lvk_area_resize_path(ctx, d_src, src_step, pix_stride, channel, srows, scols, drows, dcols, &t);
 }
 
 int lvk_hip_pyr_down(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step)

@@ -688,7 +688,7 @@ int lvk_hip_build_pyramid(lvk_hip_ctx* ctx, const void* d_img, int step, int row
                           uint8_t* levels, int16_t* derivs, int* level_rows, int* level_cols)
 {
     LVK_HIP_ENTRY(ctx);
-    LVK_HIP_REQUIRE(ctx, d_img && levels && derivs && level_rows && level_cols && rows > 0 && cols > 0);
+    LVK_HIP_REQUIRE(ctx, d_img && levels && derivs && level_rows && level_cols && rows > 0 && cols > 0 && step >= cols);
     DevicePyramid P;
     int rc;
     if ((rc = P.allocate(ctx, rows, cols, max_level, win_w, win_h)) != LVK_HIP_OK) return rc;
