@@ -1049,32 +1049,43 @@ private:
 #endif
 
 // ---------------------------------------------------------------------------------------------- Functions/Image.hpp, Filters/ScalingFilter.hpp
-// lvk::upscale (Image.cpp:155-202): EASU upsampling to `size`; size == src.size() copies.
+// lvk::upscale (Image.cpp:155-202): EASU upsampling to `size`; size == src.size() copies.  8UC3 as in the reference; 8UC1 and 8UC4 frames go through
+// lvk_hip_upscale_gray / _c4, and the output has the source's type.
 inline void upscale(const VideoFrame& src, VideoFrame& dst, const cv::Size& size, const bool yuv = true)
 {
     LVK_HIP_ASSERT(size.width >= src.cols && size.height >= src.rows);
     LVK_HIP_ASSERT(!src.empty());
+    LVK_HIP_ASSERT(src.type() == CV_8UC3 || src.type() == CV_8UC1 || src.type() == CV_8UC4);
     const auto& ctx = src.context();
     VideoFrame out;                                        // dst may be the object src refers to
-    out.create(size, CV_8UC3, ctx);
+    out.create(size, src.type(), ctx);
     hip::ContextLock lock(ctx->mutex());
-    ctx->check(lvk_hip_upscale(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols,
-                               out.device_ptr(), (int)out.step, out.rows, out.cols, yuv ? 1 : 0), "upscale");
+    // a one- or four-channel frame has no YUV form: `yuv` is not looked at (lvk_hip.h: lvk_hip_upscale_gray / _c4)
+    if (src.type() == CV_8UC1)
+        ctx->check(lvk_hip_upscale_gray(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, out.rows, out.cols), "upscale");
+    else if (src.type() == CV_8UC4)
+        ctx->check(lvk_hip_upscale_c4(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, out.rows, out.cols), "upscale");
+    else
+        ctx->check(lvk_hip_upscale(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols,
+                                   out.device_ptr(), (int)out.step, out.rows, out.cols, yuv ? 1 : 0), "upscale");
     out.timestamp = src.timestamp; out.format = src.format;
     dst = std::move(out);
 }
 
 // lvk::sharpen (Image.cpp:206-233): RCAS.  The reference's ScalingFilter passes the same frame as src and dst, where its kernel races
-// neighbour reads against writes; here the result is always that of distinct buffers (src == dst goes through a fresh frame).
+// neighbour reads against writes; here the result is always that of distinct buffers (src == dst goes through a fresh frame).  8UC1 and 8UC4 frames go
+// through lvk_hip_sharpen_gray / _c4 (the alpha byte is copied).
 inline void sharpen(const VideoFrame& src, VideoFrame& dst, const float sharpness = 0.7f)
 {
     LVK_HIP_ASSERT(sharpness >= 0.0f && sharpness <= 1.0f);
     LVK_HIP_ASSERT(!src.empty());
+    LVK_HIP_ASSERT(src.type() == CV_8UC3 || src.type() == CV_8UC1 || src.type() == CV_8UC4);
     const auto& ctx = src.context();
     VideoFrame out;
-    out.create(src.size(), CV_8UC3, ctx);
+    out.create(src.size(), src.type(), ctx);
     hip::ContextLock lock(ctx->mutex());
-    ctx->check(lvk_hip_sharpen(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, sharpness), "sharpen");
+    const auto entry = src.type() == CV_8UC1 ? lvk_hip_sharpen_gray : src.type() == CV_8UC4 ? lvk_hip_sharpen_c4 : lvk_hip_sharpen;
+    ctx->check(entry(ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, out.device_ptr(), (int)out.step, sharpness), "sharpen");
     out.timestamp = src.timestamp; out.format = src.format;
     dst = std::move(out);
 }

@@ -125,8 +125,8 @@ int lvk_hip_remap_map(lvk_hip_ctx* ctx, const void* d_src, int src_step, int row
  * reach the weights and are identical.
  * lvk_hip_set_remap_precision governs the stateless three-channel remap entries of THIS context: lvk_hip_remap_homography / _mesh / _map,
  * lvk_hip_warpmesh_apply, lvk_hip_warpmesh_apply_lens and lvk_hip_warpmesh_apply_yuv420.  A stabilizer has its own setting
- * (lvk_hip_stab_set_remap_precision) and is created EXACT whatever its context says.  Exact in every mode: the one-channel remaps of PART 2,
- * lvk_hip_upscale, lvk_hip_fsr_easu, lvk_hip_sharpen.  An unknown value is refused with LVK_HIP_ERR_ARG and changes nothing; get returns the
+ * (lvk_hip_stab_set_remap_precision) and is created EXACT whatever its context says.  Exact in every mode: the one- and four-channel remaps of PART 2,
+ * lvk_hip_upscale and lvk_hip_sharpen with their `_gray` / `_c4` forms, lvk_hip_fsr_easu.  An unknown value is refused with LVK_HIP_ERR_ARG and changes nothing; get returns the
  * current value (LVK_HIP_ERR_ARG for a NULL context). */
 #define LVK_REMAP_EXACT 0   /* bit-identical to the reference's kernels compiled for this chip (default) */
 #define LVK_REMAP_1LSB  1   /* every output byte within 1 of EXACT; fewer instructions */
@@ -607,6 +607,27 @@ int  lvk_hip_stab_push_c4(lvk_hip_stab* stab, const void* d_frame, int step, int
  * by lvk_hip_stab_push_c4 still queued (and the reverse), and a push while frames announced through lvk_hip_stab_prefetch_yuv420_host are outstanding. */
 int  lvk_hip_stab_push_c4_host(lvk_hip_stab* stab, const void* h_frame, int step, int rows, int cols, uint64_t timestamp, int format,
                                void* oh_out, int out_step, int out_rows, int* produced, uint64_t* out_timestamp, lvk_frame_info* emitted);
+
+/* ---- lvk::ScalingFilter on one- and four-channel frames: EASU upscale and RCAS of what the GRAY and four-channel pushes above emit --------------------
+ * The reference's lvk::upscale and lvk::sharpen assert CV_8UC3 (Functions/Image.cpp:159,208).  DEFINITIONS, each through the
+ * three-channel program of PART 1:
+ *   upscale, GRAY: channel 0 of lvk_hip_upscale with yuv = 0 (the easu_scale program whose luma is channel 0) on (g, c, c), for any constant c;
+ *   upscale, four channels (c0, c1, c2, a): bytes 0 .. 2 are lvk_hip_upscale with yuv = 0 on (c0, c1, c2), byte 3 is its channel 1 on (c0, a, a) -- the alpha
+ *     is resampled under the colour's weights, as in the four-channel remaps.  No `yuv` argument: there is no four-channel YUV format, and
+ *     ScalingFilterSettings::yuv_input is ignored for these frames;
+ *   sharpen, GRAY: any channel of lvk_hip_sharpen on (g, g, g) -- the rcas program with one channel, lobe = min(max(lobe_0, -0.1875), 0) * sharp; a NaN
+ *     limiter (0 x inf at a saturated ring) loses against -0.1875;
+ *   sharpen, four channels: bytes 0 .. 2 are lvk_hip_sharpen on (c0, c1, c2), byte 3 is the SOURCE pixel's alpha, copied: the limiter is built from the
+ *     colour channels and bounds only them, so a lobe applied to alpha could leave [0, 1] and wrap in the truncating conversion, and alpha cannot join the
+ *     limiter, whose three lobes are coupled through their maximum, without changing the colours.  Border pixels are copied, alpha included.
+ * All four are asynchronous on the context's stream, out of place and exact in every remap precision.  Refused with LVK_HIP_ERR_ARG, the destination
+ * untouched: a NULL pointer, rows or cols <= 0, a step below BPP * cols, a destination smaller than the source in either dimension (upscale; the same size
+ * copies), sharpness outside [0, 1] or NaN, source and destination byte ranges that overlap, and for `_c4` a base or pitch that is not a multiple of 4.
+ * `_gray` takes any base address and any pitch. */
+int lvk_hip_upscale_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step, int dst_rows, int dst_cols);
+int lvk_hip_upscale_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step, int dst_rows, int dst_cols);
+int lvk_hip_sharpen_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step, float sharpness);
+int lvk_hip_sharpen_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step, float sharpness);
 
 /* Which schedule the pushes of this filter took so far.  The library picks per push, from what it sees the caller doing (is the bulk stream still
  * busy with the previous remap? did this push begin within 15 us of the last one's return?), between the schedule of a FREE-RUNNING caller

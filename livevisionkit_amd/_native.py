@@ -62,6 +62,10 @@ _SIG = {
                                              _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _P]),
     "lvk_hip_upscale": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_sharpen": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
+    "lvk_hip_upscale_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_upscale_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_sharpen_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
+    "lvk_hip_sharpen_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
     "lvk_hip_native_rcp": (_c.c_int, [_P, _P, _P, _c.c_size_t]),
     "lvk_hip_mesh_solver_create": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _c.c_int, _c.POINTER(_P)]),
     "lvk_hip_mesh_solver_destroy": (None, [_P]),

@@ -100,7 +100,7 @@ class Context:
     def set_remap_precision(self, precision):
         """REMAP_EXACT (default: bit-identical to the reference's kernels) or REMAP_1LSB (regrouped tap weights: fewer instructions, every byte within 1)
         for the three-channel remaps of this context: remap_homography / _mesh / _map, warpmesh_apply and its lens / 4:2:0 forms.  Stabilizers have
-        their own setting; upscale, sharpen and the one-channel remaps are exact in both."""
+        their own setting; upscale, sharpen (every pixel size) and the one- and four-channel remaps are exact in both."""
         self._check(self.lib.lvk_hip_set_remap_precision(self.handle, _remap_precision(precision)))
 
     @property
@@ -402,6 +402,35 @@ class Context:
         self._check(self.lib.lvk_hip_sharpen(self.handle, src.data_ptr(), src.stride(0), rows, cols, out.data_ptr(), out.stride(0),
                                              float(sharpness)))
         return out
+
+    # ---- ScalingFilter's two steps on one-channel ([rows, cols]) and four-channel ([rows, cols, 4]; 4-byte aligned, pitches multiples of 4) frames ----
+    def _px_upscale(self, sfx, src, size, out):
+        out = self._px_out(sfx, src, out, (int(size[1]), int(size[0])))
+        self._check(getattr(self.lib, "lvk_hip_upscale" + sfx)(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1],
+                                                               out.data_ptr(), out.stride(0), out.shape[0], out.shape[1]))
+        return out
+
+    def _px_sharpen(self, sfx, src, sharpness, out):
+        out = self._px_out(sfx, src, out)
+        self._check(getattr(self.lib, "lvk_hip_sharpen" + sfx)(self.handle, src.data_ptr(), src.stride(0), src.shape[0], src.shape[1],
+                                                               out.data_ptr(), out.stride(0), float(sharpness)))
+        return out
+
+    def upscale_gray(self, src, size, out=None):
+        """lvk_hip_upscale_gray: EASU upsampling of a one-channel frame to size = (width, height): channel 0 of upscale(yuv=False) on (g, c, c)."""
+        return self._px_upscale("_gray", src, size, out)
+
+    def upscale_c4(self, src, size, out=None):
+        """lvk_hip_upscale_c4: EASU upsampling of a four-channel frame; the alpha is resampled under the colour's weights."""
+        return self._px_upscale("_c4", src, size, out)
+
+    def sharpen_gray(self, src, sharpness=0.7, out=None):
+        """lvk_hip_sharpen_gray: RCAS of a one-channel frame, out of place: any channel of sharpen on (g, g, g)."""
+        return self._px_sharpen("_gray", src, sharpness, out)
+
+    def sharpen_c4(self, src, sharpness=0.7, out=None):
+        """lvk_hip_sharpen_c4: RCAS of the three colour bytes of a four-channel frame, out of place; the alpha byte is the source pixel's."""
+        return self._px_sharpen("_c4", src, sharpness, out)
 
     def mesh_solver(self, cols, rows, gen_region=(480, 270), temporal=1.0, local=20.0, max_points=4096):
         """FrameTracker's local-motion solver (stage a10) as an object with .solve(tracked, matched, ...), .reset(), .close()."""

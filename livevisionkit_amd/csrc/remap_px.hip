@@ -1,5 +1,6 @@
 // Dense remap of ONE-channel (8UC1, VideoFrame::GRAY) and FOUR-channel (8UC4, VideoFrame::BGRA / RGBA; BGRX is a BGRA frame) frames for gfx950: the kernels
-// and launchers behind lvk_hip_remap_*_gray / _c4, lvk_hip_warpmesh_apply*_gray / _c4 and the stabilizer's GRAY and four-channel pushes.
+// and launchers behind lvk_hip_remap_*_gray / _c4, lvk_hip_warpmesh_apply*_gray / _c4, lvk_hip_upscale_gray / _c4 and the stabilizer's GRAY and
+// four-channel pushes.
 //
 // The reference's lvk::remap asserts CV_8UC3 (Functions/Image.cpp:32), so there is no one- or four-channel program to copy: each family is DEFINED from the
 // three-channel non-YUV EASU program (above its pixel trait below; DESIGN.md sections 19 and 21) and runs easu_core (remap_core.hpp, the three-channel core,
@@ -250,6 +251,17 @@ void k_remap_map_px(const uint8_t* __restrict__ src, int src_step, int rows, int
     remap_strip_px<Pix>(src, src_step, rows, cols, dst, dst_step, rows, cols, MapCoord{map, map_step}, bg);
 }
 
+// lvk::upscale on a one- or four-channel frame (easu_scale, FSR.cl:324-358, defined for these frames as the remaps above are: DESIGN.md section 22): the same
+// strip body under ScaleCoord; the source coordinate never leaves the image, so the border band is the nearest copy and the background is unreachable.
+// Exact in every remap precision: it has no 1-LSB twin, like k_easu_scale.
+template <class Pix>
+__global__ __launch_bounds__(256) LVK_REMAP_ATTR
+void k_easu_scale_px(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
+                     uint8_t* __restrict__ dst, int dst_step, int dst_rows, int dst_cols, float rsx, float rsy)
+{
+    remap_strip_px<Pix>(src, src_step, src_rows, src_cols, dst, dst_step, dst_rows, dst_cols, ScaleCoord{rsx, rsy}, 0u);
+}
+
 // The forms of family K for pixel PIX as launch_remap() takes them, [persistent grid][1-LSB][lens]: no twin, so both precisions are the one kernel (and a
 // precision that is neither, which these launchers do not check, runs it too).  Here and not in remap_core.hpp: these kernels are plain templates on
 // <Pix, LENS, CO>, not products of LVK_REMAP_KERNEL
@@ -308,6 +320,25 @@ int launch_warpmesh_apply_lens(lvk_hip_ctx* ctx, const void* d_src, int src_step
     return route_warpmesh(ctx, mesh, mesh_rows, mesh_cols, rows, cols,
                           [&](const float H[9]) { return launch_homography<Pix>(ctx, d_src, src_step, rows, cols, d_dst, dst_step, rows, cols, 0, 0, H, bg, o); },
                           [&] { return launch_mesh<Pix>(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, o); });
+}
+
+// lvk::upscale(src, dst, size) on a one- or four-channel frame: the host side of lvk_launch_upscale (remap.hip)
+template <class Pix>
+int launch_upscale(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step, int dst_rows, int dst_cols)
+{
+    LVK_HIP_REQUIRE(ctx, planes_ok<Pix>(d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols));
+    LVK_HIP_REQUIRE(ctx, dst_cols >= src_cols && dst_rows >= src_rows);                         // Image.cpp:157
+    if (dst_cols == src_cols && dst_rows == src_rows)                                           // Image.cpp:162-166
+    {
+        LVK_HIP_CHECK(ctx, hipMemcpy2DAsync(d_dst, (size_t)dst_step, d_src, (size_t)src_step, Pix::BPP * (size_t)src_cols, (size_t)src_rows,
+                                            hipMemcpyDeviceToDevice, ctx->stream));
+        return LVK_HIP_OK;
+    }
+    const float rsx = (float)src_cols / (float)dst_cols, rsy = (float)src_rows / (float)dst_rows;
+    hipLaunchKernelGGL(k_easu_scale_px<Pix>, remap_grid(dst_rows, px_span(dst_cols)), dim3(256), 0, ctx->stream, (const uint8_t*)d_src, src_step, src_rows, src_cols,
+                       (uint8_t*)d_dst, dst_step, dst_rows, dst_cols, rsx, rsy);
+    LVK_HIP_CHECK(ctx, hipGetLastError());
+    return LVK_HIP_OK;
 }
 
 } // namespace
@@ -440,6 +471,18 @@ int lvk_hip_warpmesh_apply_lens_c4(lvk_hip_ctx* ctx, const void* d_src, int src_
     const int rc = lens_args_of(ctx, lens, rows, cols, a);
     if (rc != LVK_HIP_OK) return rc;
     return launch_warpmesh_apply_lens<C4Pix>(ctx, d_src, src_step, rows, cols, d_dst, dst_step, mesh, mesh_rows, mesh_cols, bg, RemapLaunch{ctx->stream, LVK_REMAP_EXACT, &a});
+}
+
+int lvk_hip_upscale_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step, int dst_rows, int dst_cols)
+{
+    LVK_HIP_ENTRY(ctx);
+    return launch_upscale<GrayPix>(ctx, d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols);
+}
+
+int lvk_hip_upscale_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step, int dst_rows, int dst_cols)
+{
+    LVK_HIP_ENTRY(ctx);
+    return launch_upscale<C4Pix>(ctx, d_src, src_step, src_rows, src_cols, d_dst, dst_step, dst_rows, dst_cols);
 }
 
 } // extern "C"
