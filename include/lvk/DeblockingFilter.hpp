@@ -1,7 +1,9 @@
 // lvk::DeblockingFilter of the C++ facade (Filters/DeblockingFilter.{hpp,cpp}) over lvk_hip_deblock_* of lvk_hip.h: same names, settings
 // and defaults.  apply(frame, frame) deblocks in place, as the OBS plugin's ADB filter calls it (Modules/OBS-Plugin/Sources/Enhancement/
 // ADBFilter.cpp:130-136: apply(frame, frame, true), then draw_influence(frame) in test mode); the filter chains in CompositeFilter and takes the
-// frames FrameIngest::upload_obs_frame makes.  Included by LiveVisionKit.hpp.
+// frames FrameIngest::upload_obs_frame makes.  filter() dispatches on the frame's type: 8UC3 (BGR / RGB / YUV), 8UC1 of format GRAY and 8UC4 of format
+// BGRA / RGBA (lvk_hip_deblock_apply_gray / _c4: the reference's calls per channel, alpha included); draw_influence is 8UC3 only, like the reference's,
+// whose overlay is an 8UC3 buffer (DeblockingFilter.cpp:120).  Included by LiveVisionKit.hpp.
 #pragma once
 
 #include "LiveVisionKit.hpp"
@@ -48,6 +50,7 @@ public:
     void draw_influence(VideoFrame& frame) const                                  // DeblockingFilter.cpp:114-131
     {
         LVK_HIP_ASSERT(m_Handle != nullptr && !frame.empty());
+        LVK_HIP_ASSERT(frame.type() == CV_8UC3);
         run(frame, [&] {
             m_Ctx->check(lvk_hip_deblock_draw_influence(m_Handle, frame.device_ptr(), (int)frame.step, frame.rows, frame.cols, (int)frame.format),
                          "DeblockingFilter::draw_influence");
@@ -72,6 +75,9 @@ private:
     void filter(VideoFrame&& input, VideoFrame& output) override                  // DeblockingFilter.cpp:48-110, in place
     {
         LVK_HIP_ASSERT(!input.empty());
+        const int type = input.type();
+        LVK_HIP_ASSERT(type == CV_8UC3 || (type == CV_8UC1 && input.format == VideoFrame::GRAY)
+                       || (type == CV_8UC4 && (input.format == VideoFrame::BGRA || input.format == VideoFrame::RGBA)));
         VideoFrame frame = std::move(input);
         if (!m_Handle)
         {
@@ -81,7 +87,11 @@ private:
             m_Ctx->check(lvk_hip_deblock_create(m_Ctx->get(), &s, &m_Handle), "DeblockingFilter");
         }
         run(frame, [&] {
-            m_Ctx->check(lvk_hip_deblock_apply(m_Handle, frame.device_ptr(), (int)frame.step, frame.rows, frame.cols, (int)frame.format, nullptr),
+            void* p = frame.device_ptr();
+            const int step = (int)frame.step, rows = frame.rows, cols = frame.cols;
+            m_Ctx->check(type == CV_8UC1   ? lvk_hip_deblock_apply_gray(m_Handle, p, step, rows, cols, nullptr)
+                         : type == CV_8UC4 ? lvk_hip_deblock_apply_c4(m_Handle, p, step, rows, cols, (int)frame.format, nullptr)
+                                           : lvk_hip_deblock_apply(m_Handle, p, step, rows, cols, (int)frame.format, nullptr),
                          "DeblockingFilter::filter");
         });
         output = std::move(frame);

@@ -452,7 +452,8 @@ void lvk_hip_deblock_destroy(lvk_hip_deblock* deb);
  * of format LVK_FORMAT_BGR, _RGB or _YUV.  Only the region of whole block_size x block_size macroblocks at the top left is written; *region_xywh
  * (optional) = that region.  Refused with LVK_HIP_ERR_ARG before anything changes (frame and filter as they were): GRAY and 4-channel formats,
  * a frame without one whole macroblock or whose 1 / filter_scaling downscale is empty (the reference throws from cv::resize), filter_size > 255.
- * Asynchronous on the context's stream; the first call at a new geometry builds its interpolation tables. */
+ * Asynchronous on the context's stream; the first call at a new geometry builds its interpolation tables.  GRAY and BGRA / RGBA frames go through
+ * lvk_hip_deblock_apply_gray / _c4 of PART 2, on the same handle. */
 int  lvk_hip_deblock_apply(lvk_hip_deblock* deb, void* d_frame, int step, int rows, int cols, int format, int region_xywh[4]);
 /* DeblockingFilter::draw_influence (:114-131): blends MAGENTA[format] into the region of the last apply with that apply's blend maps.  Refused
  * before the first apply and when that region does not fit the frame. */
@@ -628,6 +629,10 @@ int lvk_hip_upscale_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int 
 int lvk_hip_upscale_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int src_rows, int src_cols, void* d_dst, int dst_step, int dst_rows, int dst_cols);
 int lvk_hip_sharpen_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step, float sharpness);
 int lvk_hip_sharpen_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step, float sharpness);
+
+/* ---- lvk::DeblockingFilter on one- and four-channel frames ------------------------------------------------------------------------------------------
+ * The GRAY and BGRA / RGBA forms of lvk_hip_deblock_apply, on the same handle, are declared in lvk_hip_deblock_px.h, which this header includes at its
+ * end: a host that includes lvk_hip.h sees them like every other entry of PART 2. */
 
 /* Which schedule the pushes of this filter took so far.  The library picks per push, from what it sees the caller doing (is the bulk stream still
  * busy with the previous remap? did this push begin within 15 us of the last one's return?), between the schedule of a FREE-RUNNING caller
@@ -838,4 +843,6 @@ int lvk_hip_area_resize_path(lvk_hip_ctx* ctx, const void* d_src, int src_step, 
 #ifdef __cplusplus
 }
 #endif
+
+#include "lvk_hip_deblock_px.h"   /* lvk_hip_deblock_apply_gray / _c4 (PART 2) */
 #endif /* LVK_HIP_H */

@@ -167,11 +167,23 @@ _SIG = {
     "lvk_hip_area_resize_path": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
 }
 
+# what include/lvk_hip_deblock_px.h declares (lvk_hip.h includes it; the header has its own pin, tests/test_deblock_px_spec.py)
+_SIG_DEBLOCK_PX = {
+    "lvk_hip_deblock_apply_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+    "lvk_hip_deblock_apply_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+}
+
 _lib = None
 
 
 def symbols():
+    """The names include/lvk_hip.h itself declares."""
     return sorted(_SIG.keys())
+
+
+def symbols_deblock_px():
+    """The names include/lvk_hip_deblock_px.h declares."""
+    return sorted(_SIG_DEBLOCK_PX.keys())
 
 
 def load():
@@ -185,7 +197,7 @@ def load():
             "(or `make -C livevisionkit_amd/csrc`). There is no CPU fallback.")
     import torch  # noqa: F401  (loads the process-wide HIP runtime first)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in _SIG.items():
+    for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX}.items():
         fn = getattr(lib, name)      # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -10,19 +10,11 @@
 //   k_deblock_blend    rebuilds `smooth` (8U bilinear from the median frame) and `keep` (float bilinear from keep_block) per pixel and
 //                      writes the blend in place; the full-size smooth / keep / deblock frames of the reference are never materialised.
 // draw_influence is k_deblock_blend with a constant colour for `smooth` and the keep_block of the last apply.
-#include "lvk_hip_internal.hpp"
+#include "deblock_internal.hpp"
 
-#include <cmath>
-#include <algorithm>
-#include <vector>
-
-int lvk_get_lin8tab(lvk_hip_ctx* ctx, int ssize, int dsize, bool vertical, const Lin8Entry** d_out);   // ingest.hip
+using namespace lvk_deblock;        // the handle's host side, shared with deblock_px.hip
 
 namespace {
-
-constexpr int kMaxFilterSize = 255;       // apply refuses larger windows (declared deviation)
-constexpr int kMedTile = 16;              // median: 16 x 16 outputs per block
-constexpr int kMedLdsMaxK = 113;          // (16 + k - 1)^2 packed pixels fit 64 KiB of LDS up to this k; larger k read global memory
 
 __device__ __forceinline__ int gray_of(const uint8_t* p, int fmt)
 {
@@ -250,94 +242,9 @@ void k_deblock_blend(uint8_t* __restrict__ frame, int step, int rh, int rw,
     p[2] = (uint8_t)sat_u8(((float)c2 * keep + (float)s2 * deb) / den);
 }
 
-// computeResizeAreaTab for a scale given by the caller (the 1 / filter_scaling downscale: scale = 1 / (double)(1.f / s), not ssize / dsize)
-void area_tab(int ssize, int dsize, double scale, std::vector<int2>& range, std::vector<AreaTabEntry>& tab)
-{
-    range.assign((size_t)dsize, int2{0, 0});
-    tab.clear();
-    for (int dx = 0; dx < dsize; dx++)
-    {
-        const double fsx1 = dx * scale, fsx2 = fsx1 + scale;
-        const double cell = std::min(scale, ssize - fsx1);
-        int sx1 = (int)std::ceil(fsx1), sx2 = (int)std::floor(fsx2);
-        sx2 = std::min(sx2, ssize - 1);
-        sx1 = std::min(sx1, sx2);
-        const int start = (int)tab.size();
-        if (sx1 - fsx1 > 1e-3) tab.push_back({sx1 - 1, (float)((sx1 - fsx1) / cell)});
-        for (int sx = sx1; sx < sx2; sx++) tab.push_back({sx, (float)(1.0 / cell)});
-        if (fsx2 - sx2 > 1e-3) tab.push_back({sx2, (float)(std::min(std::min(fsx2 - sx2, 1.0), cell) / cell)});
-        range[(size_t)dx] = int2{start, (int)tab.size() - start};
-    }
-}
-
 bool settings_valid(const lvk_deblock_settings& s)
 {
     return s.block_size > 0 && s.filter_size >= 3 && s.filter_size % 2 == 1 && s.detection_levels > 0 && s.filter_scaling > 1.0f;
-}
-
-int small_extent(int n, float scaling)          // saturate_cast<int>(n * (double)(1.f / s)); 0 where it does not fit an int
-{
-    const double v = std::rint((double)n * (double)(1.0f / scaling));
-    return v >= 1.0 && v <= 2147483647.0 ? (int)v : 0;
-}
-
-} // namespace
-
-struct lvk_hip_deblock
-{
-    lvk_hip_ctx* ctx = nullptr;
-    lvk_deblock_settings settings{};
-    // geometry of the last apply (draw_influence reuses its maps)
-    int rh = 0, rw = 0, ey = 0, ex = 0, hs = 0, ws = 0;
-    bool have_maps = false;
-    // device buffers, sized for the geometry they were last allocated for (lvk_hip_malloc pool of the context)
-    uint8_t* d_small = nullptr; uint8_t* d_median = nullptr; size_t small_cap = 0, median_cap = 0;
-    uint8_t* d_grid = nullptr; float* d_keep = nullptr; size_t grid_cap = 0, keep_cap = 0;       // d_grid: mean (cells) | grid (cells)
-    // area tables of the non-integer downscale, keyed by (rh, rw, hs, ws, scale)
-    int2* d_range = nullptr; AreaTabEntry* d_tab = nullptr; size_t range_cap = 0, tab_cap = 0;
-    int2* d_xr = nullptr; int2* d_yr = nullptr; AreaTabEntry* d_xt = nullptr; AreaTabEntry* d_yt = nullptr;
-    int tab_rh = -1, tab_rw = -1, tab_hs = -1, tab_ws = -1; double tab_scale = 0.0;
-
-    void release()
-    {
-        lvk_hip_free(ctx, d_small); lvk_hip_free(ctx, d_median); lvk_hip_free(ctx, d_grid); lvk_hip_free(ctx, d_keep);
-        lvk_hip_free(ctx, d_range); lvk_hip_free(ctx, d_tab);
-        d_small = d_median = d_grid = nullptr; d_keep = nullptr; d_range = nullptr; d_tab = nullptr;
-        small_cap = median_cap = grid_cap = keep_cap = range_cap = tab_cap = 0;
-    }
-};
-
-namespace {
-
-int ensure(lvk_hip_ctx* ctx, void** p, size_t& cap, size_t bytes)
-{
-    if (*p && cap >= bytes) return LVK_HIP_OK;
-    if (*p) { lvk_hip_free(ctx, *p); *p = nullptr; cap = 0; }
-    const int rc = lvk_hip_malloc(ctx, bytes, p);
-    if (rc == LVK_HIP_OK) cap = bytes;
-    return rc;
-}
-
-int upload_area_tabs(lvk_hip_deblock* d, int rh, int rw, int hs, int ws, double scale)
-{
-    if (d->d_range && d->tab_rh == rh && d->tab_rw == rw && d->tab_hs == hs && d->tab_ws == ws && d->tab_scale == scale) return LVK_HIP_OK;
-    std::vector<int2> xr, yr; std::vector<AreaTabEntry> xt, yt;
-    area_tab(rw, ws, scale, xr, xt);
-    area_tab(rh, hs, scale, yr, yt);
-    // one block: x ranges | y ranges, and one: x taps | y taps (each range indexes its own axis' taps)
-    std::vector<int2> ranges(xr); ranges.insert(ranges.end(), yr.begin(), yr.end());
-    std::vector<AreaTabEntry> taps(xt); taps.insert(taps.end(), yt.begin(), yt.end());
-    int rc;
-    if ((rc = ensure(d->ctx, (void**)&d->d_range, d->range_cap, ranges.size() * sizeof(int2))) != LVK_HIP_OK) return rc;
-    if ((rc = ensure(d->ctx, (void**)&d->d_tab, d->tab_cap, std::max<size_t>(taps.size(), 1) * sizeof(AreaTabEntry))) != LVK_HIP_OK) return rc;
-    // (synchronous, once per geometry -- like the context's INTER_LINEAR / INTER_AREA table caches; the host vectors die with this call)
-    LVK_HIP_CHECK(d->ctx, hipStreamSynchronize(d->ctx->stream));
-    LVK_HIP_CHECK(d->ctx, hipMemcpy(d->d_range, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice));
-    if (!taps.empty()) LVK_HIP_CHECK(d->ctx, hipMemcpy(d->d_tab, taps.data(), taps.size() * sizeof(AreaTabEntry), hipMemcpyHostToDevice));
-    d->d_xr = d->d_range; d->d_yr = d->d_range + xr.size();
-    d->d_xt = d->d_tab; d->d_yt = d->d_tab + xt.size();
-    d->tab_rh = rh; d->tab_rw = rw; d->tab_hs = hs; d->tab_ws = ws; d->tab_scale = scale;
-    return LVK_HIP_OK;
 }
 
 bool format_ok(int format) { return format == LVK_FORMAT_BGR || format == LVK_FORMAT_RGB || format == LVK_FORMAT_YUV; }

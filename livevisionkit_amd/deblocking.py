@@ -1,6 +1,7 @@
 """Host-side mirror of lvk::DeblockingFilter (reference: LiveVisionKit/Filters/DeblockingFilter.hpp:26-57) over the C-ABI.
 Same method names: configure / apply / draw_influence / filter_region.  Frames are torch uint8 tensors [rows, cols, 3] on the GPU
-(any row pitch: a view with stride(1) == 3 and stride(2) == 1), filtered IN PLACE like the reference's apply(frame, frame)."""
+(any row pitch: a view with stride(1) == 3 and stride(2) == 1), filtered IN PLACE like the reference's apply(frame, frame).  apply also takes
+GRAY frames [rows, cols] and BGRA / RGBA frames [rows, cols, 4] (lvk_hip_deblock_apply_gray / _c4)."""
 import ctypes
 
 import numpy as np
@@ -44,9 +45,19 @@ class DeblockingFilter:
         self.settings = s
 
     def apply(self, frame, fmt=FORMAT_YUV):
-        """Deblocks `frame` in place (asynchronous on the context's stream); returns the filter region (x, y, w, h)."""
+        """Deblocks `frame` in place (asynchronous on the context's stream); returns the filter region (x, y, w, h).  The tensor selects the
+        entry: [rows, cols] is a GRAY frame (`fmt` ignored), [rows, cols, 4] with stride(1) == 4 a BGRA / RGBA frame of format `fmt`, anything
+        else goes to the three-channel entry with `fmt` (which refuses GRAY / BGRA / RGBA there)."""
         region = (_c.c_int * 4)()
-        self.ctx._check(self.lib.lvk_hip_deblock_apply(self.handle, *_frame_args(frame), int(fmt), region))
+        if frame.dim() == 2:
+            if frame.stride(1) != 1 or frame.dtype.itemsize != 1:
+                raise ValueError("a packed 8UC1 frame [rows, cols] with contiguous rows is required")
+            rc = self.lib.lvk_hip_deblock_apply_gray(self.handle, frame.data_ptr(), frame.stride(0), frame.shape[0], frame.shape[1], region)
+        elif frame.dim() == 3 and frame.shape[2] == 4:
+            rc = self.lib.lvk_hip_deblock_apply_c4(self.handle, *frame_args(frame, 4, "8UC4"), frame.shape[0], frame.shape[1], int(fmt), region)
+        else:
+            rc = self.lib.lvk_hip_deblock_apply(self.handle, *_frame_args(frame), int(fmt), region)
+        self.ctx._check(rc)
         return tuple(region)
 
     def draw_influence(self, frame, fmt=FORMAT_YUV):
