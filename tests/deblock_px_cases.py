@@ -1,9 +1,11 @@
-"""Shared by the one- and four-channel deblocking tests (tests/test_deblock_px_spec.py, tests/test_deblock_px_gpu.py): the cases, their input
-textures and -- computed once per case -- what the specification (tests/np_deblock_px.py) makes of them."""
+"""Shared by the one- and four-channel deblocking tests (tests/test_deblock_px_spec.py, tests/test_deblock_px_gpu.py) and by the three-channel tests
+that run the same small and edge cases (tests/test_deblock_spec.py, tests/test_deblock_gpu.py): the cases, their input textures and -- computed once
+per case -- what the specification (tests/np_deblock_px.py, tests/np_deblock.py) makes of them."""
 import functools
 
 import numpy as np
 
+from tests import np_deblock as nd
 from tests import np_deblock_px as npx
 
 GRAY, BGRA, RGBA = npx.FMT_GRAY, npx.FMT_BGRA, npx.FMT_RGBA
@@ -11,7 +13,7 @@ VARIANTS = [GRAY, BGRA, RGBA]
 NAMES = {GRAY: "gray", BGRA: "bgra", RGBA: "rgba"}
 
 CASES = [
-    # rows, cols, levels, block, k, scaling, pad (GRAY: bytes; four channels: pixels)
+    # rows, cols, levels, block, k, scaling, pad (GRAY: bytes; three and four channels: pixels)
     (67, 131, 3, 16, 5, 3.0, 3),        # area tables (1 / (double)(1.f / 3) != 3), register median 5, region 128 x 64 inside the frame
     (131, 67, 1, 2, 3, 2.0, 5),         # 2 x 2 (sum + 2) >> 2 both in stats and downscale, one level
     (64, 96, 3, 16, 5, 4.0, 4),         # integer box rule 4 x 4; aligned rows
@@ -61,6 +63,17 @@ def expected(case, fmt):
     c = channels_of(fmt)
     img = blocky(rows, cols, seed=rows * 7 + cols + c, block=max(bs, 2), channels=c)
     want, info = npx.deblock_px(img, fmt, levels, bs, k, s)
+    for a in (img, want):
+        a.setflags(write=False)
+    return img, want, info
+
+
+@functools.lru_cache(maxsize=None)
+def expected3(case, fmt):
+    """(input, specification's output, info) of one case as a three-channel frame of format BGR / RGB / YUV; shared between tests, never written to."""
+    rows, cols, levels, bs, k, s, _ = case
+    img = blocky(rows, cols, seed=rows * 7 + cols + 3, block=max(bs, 2), channels=3)
+    want, info = nd.deblock(img, fmt, levels, bs, k, s)
     for a in (img, want):
         a.setflags(write=False)
     return img, want, info

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from tests import deblock_px_cases as px
 from tests import np_deblock as nd
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +75,28 @@ def test_apply_and_influence_bit_exact(ctx, rows, cols, fmt, levels, bs, k, s, p
     ctx.sync()
     want_buf[:, :cols] = nd.draw_influence(want, fmt, info)
     assert np.array_equal(buf_t.cpu().numpy(), want_buf)
+    f.close()
+
+
+@pytest.mark.parametrize("fmt", [BGR, YUV], ids=["bgr", "yuv"])
+@pytest.mark.parametrize("case", px.CASES, ids=px.case_id)
+def test_small_and_edge_cases_bit_exact(ctx, case, fmt):
+    # the shapes the one- and four-channel kernels are held to (tests/deblock_px_cases.py): partial downscale cells, ex = 5, blocks smaller than a wave,
+    # the run-time-k LDS median, k = 115 from global memory, the 2 x 2 rule, the area tables
+    import livevisionkit_amd as lvk
+    img, want, info = px.expected3(case, fmt)
+    rows, cols = img.shape[:2]
+    buf_t, view, buf = device_frame(img, case[6], guard_seed=case[4])
+    f = lvk.DeblockingFilter(ctx, **settings(*case[2:6]))
+    region = f.apply(view, fmt)
+    ctx.sync()
+    assert region == info["region"] == f.filter_region()
+    want_buf = buf.copy(); want_buf[:, :cols] = want
+    got = buf_t.cpu().numpy()
+    assert np.array_equal(got, want_buf), "%d bytes differ" % int((got != want_buf).sum())     # the pitch slack's guard bytes included
+    _, _, RW, RH = region
+    assert np.array_equal(got[RH:], buf[RH:]) and np.array_equal(got[:, RW:], buf[:, RW:])      # below and right of the region: as they were
+    assert np.array_equal(f.grid()[2], info["keep_block"])
     f.close()
 
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import np_deblock as nd
+from tests.deblock_px_cases import CASES, NOT_LIVE, case_id, expected3
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -114,6 +115,19 @@ def test_bytes_outside_the_region_are_untouched():
     assert info["region"] == (0, 0, 64, 128)
     assert np.array_equal(out[128:], f[128:]) and np.array_equal(out[:, 64:], f[:, 64:])
     assert not np.array_equal(out[:128, :64], f[:128, :64])
+
+
+@pytest.mark.parametrize("fmt", [nd.FMT_BGR, nd.FMT_YUV], ids=["bgr", "yuv"])
+@pytest.mark.parametrize("case", [c for c in CASES if c[:2] != NOT_LIVE], ids=case_id)
+def test_every_small_gpu_case_is_live(case, fmt):
+    """A condition on the inputs of tests/test_deblock_gpu.py::test_small_and_edge_cases_bit_exact, not a measurement: the specification changes at
+    least 25 % of the region's bytes and keep_block takes at least two values -- a case the filter leaves (nearly) unchanged would pass whatever the
+    kernels do."""
+    img, want, info = expected3(case, fmt)
+    _, _, RW, RH = info["region"]
+    changed = want[:RH, :RW] != img[:RH, :RW]
+    assert changed.mean() >= 0.25, changed.mean()
+    assert len(np.unique(info["keep_block"])) >= 2
 
 
 def test_draw_influence_blends_magenta_where_the_filter_acts():
