@@ -1,7 +1,8 @@
 // lvk::CASFilter of the C++ facade: the OBS plugin's CAS filter (Modules/OBS-Plugin/Sources/Enhancement/CASFilter.cpp, Effects/CASEffect.cpp:
 // contrast adaptive sharpening, FidelityFX CasFilter with CAS_SLOW and CAS_BETTER_DIAGONALS) over lvk_hip_cas of lvk_hip.h.  The plugin runs
 // it as an OBS graphics effect; here it is a VideoFilter, so it chains in CompositeFilter (deblock, then sharpen) and takes the frames
-// FrameIngest::upload_obs_frame makes: BGR / RGB / YUV, and BGRA / RGBA frames of 4 channels (VideoFrame::reformat, ConversionFilter).
+// FrameIngest::upload_obs_frame makes: BGR / RGB / YUV, BGRA / RGBA frames of 4 channels (VideoFrame::reformat, ConversionFilter) and GRAY
+// frames of one channel (lvk_hip_cas_gray: channel 0 of the filter on (g, g, g)).
 // Included by LiveVisionKit.hpp.
 #pragma once
 
@@ -31,14 +32,19 @@ private:
     void filter(VideoFrame&& input, VideoFrame& output) override
     {
         LVK_HIP_ASSERT(!input.empty());
+        const bool gray = input.type() == CV_8UC1;
+        LVK_HIP_ASSERT(!gray || input.format == VideoFrame::GRAY);
         VideoFrame src = std::move(input);          // CAS reads its neighbours: out of place, into a fresh frame
         adopt(src);
         VideoFrame dst(src.timestamp);
         dst.create(src.size(), src.type(), m_Ctx);
         dst.format = src.format;
         run(src, [&] {
-            m_Ctx->check(lvk_hip_cas(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, (int)src.format, dst.device_ptr(),
-                                     (int)dst.step, m_Settings.sharpness), "CASFilter::filter");
+            m_Ctx->check(gray ? lvk_hip_cas_gray(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, dst.device_ptr(), (int)dst.step,
+                                                 m_Settings.sharpness)
+                              : lvk_hip_cas(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, (int)src.format, dst.device_ptr(),
+                                            (int)dst.step, m_Settings.sharpness),
+                         "CASFilter::filter");
         });
         output = std::move(dst);
     }

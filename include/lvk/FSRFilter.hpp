@@ -1,7 +1,8 @@
 // lvk::FSRFilter of the C++ facade: the OBS plugin's FSR filter (Modules/OBS-Plugin/Sources/Scaling/FSRFilter.cpp, Effects/FSREffect.cpp: the
 // FidelityFX FSR 1 EASU pass; the plugin leaves sharpening to the CAS filter) over lvk_hip_fsr_geometry and lvk_hip_fsr_easu of lvk_hip.h.
 // The plugin runs it as an OBS graphics effect; here it is a VideoFilter, so it chains in CompositeFilter (e.g. ConversionFilter to BGRA,
-// FSRFilter, CASFilter) and takes BGR / RGB / YUV and BGRA / RGBA frames.  The output size follows the current frame.
+// FSRFilter, CASFilter) and takes BGR / RGB / YUV and BGRA / RGBA frames, and GRAY frames of one channel (lvk_hip_fsr_easu_gray: channel 0 of the
+// pass on (g, g, g)).  The output size follows the current frame.
 // Included by LiveVisionKit.hpp.
 #pragma once
 
@@ -41,6 +42,8 @@ private:
     void filter(VideoFrame&& input, VideoFrame& output) override
     {
         LVK_HIP_ASSERT(!input.empty());
+        const bool gray = input.type() == CV_8UC1;
+        LVK_HIP_ASSERT(!gray || input.format == VideoFrame::GRAY);
         const int crop[4] = {m_Settings.crop_left, m_Settings.crop_top, m_Settings.crop_right, m_Settings.crop_bottom};
         int region[4] = {0, 0, 0, 0}, size[2] = {0, 0}, skip = 0;
         const int rc = lvk_hip_fsr_geometry(input.rows, input.cols, m_Settings.output_size.height, m_Settings.output_size.width,
@@ -57,8 +60,11 @@ private:
         dst.create(cv::Size(size[1], size[0]), src.type(), m_Ctx);
         dst.format = src.format;
         run(src, [&] {
-            m_Ctx->check(lvk_hip_fsr_easu(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, (int)src.format, region, dst.device_ptr(),
-                                          (int)dst.step, dst.rows, dst.cols), "FSRFilter::filter");
+            m_Ctx->check(gray ? lvk_hip_fsr_easu_gray(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, region, dst.device_ptr(),
+                                                      (int)dst.step, dst.rows, dst.cols)
+                              : lvk_hip_fsr_easu(m_Ctx->get(), src.device_ptr(), (int)src.step, src.rows, src.cols, (int)src.format, region,
+                                                 dst.device_ptr(), (int)dst.step, dst.rows, dst.cols),
+                         "FSRFilter::filter");
         });
         output = std::move(dst);
     }

@@ -630,6 +630,23 @@ int lvk_hip_upscale_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int sr
 int lvk_hip_sharpen_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step, float sharpness);
 int lvk_hip_sharpen_c4(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step, float sharpness);
 
+/* ---- lvk::CASFilter and lvk::FSRFilter on one-channel frames ------------------------------------------------------------------------------------------
+ * The plugin runs both filters as RGBA effects: there is no one-channel program.  DEFINITIONS, each through the three-channel
+ * specification of PART 1's entry, which keeps refusing LVK_FORMAT_GRAY itself:
+ *   CAS, GRAY: channel 0 of the three-channel CAS on (g, g, g) -- CAS sharpens every channel on its own, so this is the program with one channel; neighbours
+ *     outside the frame read as 0, the load is the correctly rounded u / 255, the store rint(v * 255);
+ *   EASU, GRAY: channel 0 of the three-channel EASU on (g, g, g), the same for BGR, RGB and YUV; region_xywh, the clamp-to-edge taps and the output size are
+ *     those of the three-channel entry, and the geometry call of PART 1 serves both.
+ * Both are asynchronous on the context's stream and out of place, at any base address and any pitch.  Refused with LVK_HIP_ERR_ARG, the destination
+ * untouched: a NULL pointer, a size <= 0, a step below its row, sharpness outside [0, 1] or NaN, an empty region or one outside the frame, source and
+ * destination byte ranges that overlap. */
+int lvk_hip_cas_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step, float sharpness);
+int lvk_hip_fsr_easu_gray(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, const int region_xywh[4],
+                          void* d_dst, int dst_step, int out_rows, int out_cols);
+/* The kernel path lvk_hip_fsr_easu_gray takes for a rw x rh region scaled to out_rows x out_cols: 0 = staged, 1 = direct (a one-channel texel is a
+ * quarter of a staged three-channel one, so more scales stay staged); LVK_HIP_ERR_ARG for a size <= 0.  Host only, for the tests. */
+int lvk_hip_fsr_easu_gray_path(int rw, int rh, int out_rows, int out_cols);
+
 /* ---- lvk::DeblockingFilter on one- and four-channel frames ------------------------------------------------------------------------------------------
  * The GRAY and BGRA / RGBA forms of lvk_hip_deblock_apply, on the same handle, are declared in lvk_hip_deblock_px.h, which this header includes at its
  * end: a host that includes lvk_hip.h sees them like every other entry of PART 2. */

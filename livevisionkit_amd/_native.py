@@ -164,6 +164,9 @@ _SIG = {
                                         _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "lvk_hip_fsr_easu_const": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)]),
     "lvk_hip_fsr_easu_path": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_cas_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_float]),
+    "lvk_hip_fsr_easu_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _P, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_fsr_easu_gray_path": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_area_resize_path": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
 }
 

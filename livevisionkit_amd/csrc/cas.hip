@@ -7,10 +7,12 @@
 //            converted once to u / 255 (correctly rounded) and staged as float32 in LDS; outside the frame the tile holds 0.  A 4-channel
 //            frame's 4th byte is not staged.
 //   compute  wave w walks rows 4w .. 4w + 3 of the tile, one pixel column per lane, with a 3 x 3 x 3 register window that takes one new
-//            tile row (3 pixels) per output row.  The arithmetic is the specification's, unfused, with the FidelityFX bit tricks.
+//            tile row (3 pixels) per output row.  The arithmetic is the specification's, unfused, with the FidelityFX bit tricks
+//            (cas_core.hpp).
 //   store    the output bytes go to a second LDS tile laid out at the destination's byte alignment, then out as aligned dwords; only the
 //            partial dwords at the two ends of a row segment are written byte by byte.  No byte outside cols * C of a row is written.
 #include "lvk_hip_internal.hpp"
+#include "cas_core.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -30,35 +32,7 @@ template <int C> struct CasTile
     static constexpr int out_dwords = out_stride / 4;
 };
 
-__device__ __forceinline__ float as_f(uint32_t u) { return __uint_as_float(u); }
-__device__ __forceinline__ uint32_t as_u(float f) { return __float_as_uint(f); }
-
-// correctly rounded u / 255: q = u * (1 / 255), then one exact-residual correction (Markstein); checked for all 256 values by
-// tests/test_cas_spec.py against the exact rational quotient
-__device__ __forceinline__ float unit_of(float u)
-{
-    const float c = 1.0f / 255.0f;
-    const float q = u * c;
-    return __builtin_fmaf(__builtin_fmaf(-q, 255.0f, u), c, q);
-}
-
-__device__ __forceinline__ float sat(float v) { return __builtin_fminf(__builtin_fmaxf(v, 0.0f), 1.0f); }
-
-// One channel of CasFilter: the nine neighbours in the order a b c / d e f / g h i.
-__device__ __forceinline__ float cas_channel(float a, float b, float c, float d, float e, float f, float g, float h, float i, float peak)
-{
-    float mn = __builtin_fminf(__builtin_fminf(d, e), __builtin_fminf(f, __builtin_fminf(b, h)));
-    float mx = __builtin_fmaxf(__builtin_fmaxf(d, e), __builtin_fmaxf(f, __builtin_fmaxf(b, h)));
-    mn = mn + __builtin_fminf(__builtin_fminf(mn, a), __builtin_fminf(c, __builtin_fminf(g, i)));
-    mx = mx + __builtin_fmaxf(__builtin_fmaxf(mx, a), __builtin_fmaxf(c, __builtin_fmaxf(g, i)));
-    const float lo_rcp_mx = as_f(0x7ef07ebbu - as_u(mx));
-    const float amp = as_f((as_u(sat(__builtin_fminf(mn, 2.0f - mx) * lo_rcp_mx)) >> 1) + 0x1fbc4639u);
-    const float w = amp * peak;
-    const float wt = 1.0f + 4.0f * w;
-    const float r = as_f(0x7ef19fffu - as_u(wt));
-    const float med_rcp = r * ((-r) * wt + 2.0f);
-    return sat(((((b * w + d * w) + f * w) + h * w) + e) * med_rcp);
-}
+using namespace ffx;                       // unit_of, sat, to_byte, cas_channel: the arithmetic, shared with cas_gray.hip
 
 template <int C>
 __global__ __launch_bounds__(256)
@@ -135,7 +109,7 @@ void k_cas(const uint8_t* __restrict__ src, long long src_step, int rows, int co
                 {
                     const float v = cas_channel(win[0][0][c], win[0][1][c], win[0][2][c], win[1][0][c], win[1][1][c], win[1][2][c],
                                                 win[2][0][c], win[2][1][c], win[2][2][c], peak);
-                    orow[c] = (uint8_t)(uint32_t)rintf(v * 255.0f);
+                    orow[c] = (uint8_t)to_byte(v);
                 }
                 if (C == 4) orow[3] = 255;
             }

@@ -12,6 +12,7 @@
 // The arithmetic is the specification's, unfused, with the FidelityFX bit tricks and a correctly rounded 1 / aW.  Output bytes are
 // stored one channel at a time (a whole dword for 4-channel pixels at an aligned address): no byte outside out_cols * C of a row is written.
 #include "lvk_hip_internal.hpp"
+#include "fsr_core.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -19,9 +20,8 @@
 
 namespace {
 
-constexpr int kTileW = 64;                 // output columns per tile (one per lane)
-constexpr int kTileH = 16;                 // output rows per tile (4 per wave)
-constexpr int kRowsPerWave = kTileH / 4;
+using namespace ffx;                       // the tile, the luma-only analysis, the tap weights, the byte conversions (fsr_core.hpp): shared with fsr_gray.hip
+
 constexpr int kStagePixels = 2560;         // LDS budget of the staged path: 40 KiB of float4, four blocks per CU
 
 struct EasuArgs
@@ -37,62 +37,17 @@ struct EasuArgs
     int ri, bi;                            // byte of the shader's r and b (g is byte 1)
 };
 
-__device__ __forceinline__ float as_f(uint32_t u) { return __uint_as_float(u); }
-__device__ __forceinline__ uint32_t as_u(float f) { return __float_as_uint(f); }
-__device__ __forceinline__ float lo_rcp(float v) { return as_f(0x7ef07ebbu - as_u(v)); }
-__device__ __forceinline__ float lo_rsq(float v) { return as_f(0x5f347d74u - (as_u(v) >> 1)); }
-__device__ __forceinline__ float sat(float v) { return __builtin_fminf(__builtin_fmaxf(v, 0.0f), 1.0f); }
-
-// correctly rounded u / 255 (the CAS load, tests/test_cas_spec.py checks the correction for all 256 values)
-__device__ __forceinline__ float unit_of(uint32_t u)
-{
-    const float c = 1.0f / 255.0f, x = (float)u;
-    const float q = x * c;
-    return __builtin_fmaf(__builtin_fmaf(-q, 255.0f, x), c, q);
-}
-
 // (r, g, b, luma) of the texel at byte p of the frame
 __device__ __forceinline__ float4 texel(const uint8_t* p, int ri, int bi)
 {
-    const float r = unit_of(p[ri]), g = unit_of(p[1]), b = unit_of(p[bi]);
+    const float r = unit_of((float)p[ri]), g = unit_of((float)p[1]), b = unit_of((float)p[bi]);
     return make_float4(r, g, b, b * 0.5f + (r * 0.5f + g));
 }
 
-// FsrEasuSetF: one bilinear corner's contribution to the direction and the length
-__device__ __forceinline__ void easu_set(float& dirx, float& diry, float& len, float w, float lA, float lB, float lC, float lD, float lE)
-{
-    const float dc = lD - lC, cb = lC - lB;
-    float lenx = lo_rcp(__builtin_fmaxf(__builtin_fabsf(dc), __builtin_fabsf(cb)));
-    const float dx = lD - lB;
-    dirx = dirx + dx * w;
-    lenx = sat(__builtin_fabsf(dx) * lenx);
-    lenx = lenx * lenx;
-    len = len + lenx * w;
-    const float ec = lE - lC, ca = lC - lA;
-    float leny = lo_rcp(__builtin_fmaxf(__builtin_fabsf(ec), __builtin_fabsf(ca)));
-    const float dy = lE - lA;
-    diry = diry + dy * w;
-    leny = sat(__builtin_fabsf(dy) * leny);
-    leny = leny * leny;
-    len = len + leny * w;
-}
-
 // FsrEasuTapF for the tap at (ox, oy) from 'f'
-__device__ __forceinline__ void easu_tap(float3& ac, float& aw, float ox, float oy, float ppx, float ppy, float dirx, float diry, float len2x,
-                                         float len2y, float lob, float clp, float4 c)
+__device__ __forceinline__ void easu_tap(float3& ac, float& aw, float ox, float oy, float ppx, float ppy, const EasuLobe& lobe, float4 c)
 {
-    const float offx = ox - ppx, offy = oy - ppy;
-    float vx = (offx * dirx) + (offy * diry);
-    float vy = (offx * (-diry)) + (offy * dirx);
-    vx = vx * len2x;
-    vy = vy * len2y;
-    const float d2 = __builtin_fminf(vx * vx + vy * vy, clp);
-    float wb = 0.4f * d2 + -1.0f;
-    float wa = lob * d2 + -1.0f;
-    wb = wb * wb;
-    wa = wa * wa;
-    wb = 1.5625f * wb + -0.5625f;
-    const float w = wb * wa;
+    const float w = easu_weight(ox, oy, ppx, ppy, lobe);
     ac.x = ac.x + c.x * w;
     ac.y = ac.y + c.y * w;
     ac.z = ac.z + c.z * w;
@@ -104,39 +59,21 @@ __device__ __forceinline__ float3 easu(const float4 (&t)[4][4], float ppx, float
 {
     const float4 b = t[0][1], c = t[0][2], e = t[1][0], f = t[1][1], g = t[1][2], h = t[1][3];
     const float4 i = t[2][0], j = t[2][1], k = t[2][2], l = t[2][3], n = t[3][1], o = t[3][2];
-    float dirx = 0.0f, diry = 0.0f, len = 0.0f;
-    easu_set(dirx, diry, len, (1.0f - ppx) * (1.0f - ppy), b.w, e.w, f.w, g.w, j.w);
-    easu_set(dirx, diry, len, ppx * (1.0f - ppy), c.w, f.w, g.w, h.w, k.w);
-    easu_set(dirx, diry, len, (1.0f - ppx) * ppy, f.w, i.w, j.w, k.w, n.w);
-    easu_set(dirx, diry, len, ppx * ppy, g.w, j.w, k.w, l.w, o.w);
-    const float dir2x = dirx * dirx, dir2y = diry * diry;
-    float dirr = dir2x + dir2y;
-    const bool zro = dirr < (1.0f / 32768.0f);
-    dirr = zro ? 1.0f : lo_rsq(dirr);
-    dirx = zro ? 1.0f : dirx;
-    dirx = dirx * dirr;
-    diry = diry * dirr;
-    len = len * 0.5f;
-    len = len * len;
-    const float stretch = (dirx * dirx + diry * diry) * lo_rcp(__builtin_fmaxf(__builtin_fabsf(dirx), __builtin_fabsf(diry)));
-    const float len2x = 1.0f + (stretch - 1.0f) * len;
-    const float len2y = 1.0f + -0.5f * len;
-    const float lob = 0.5f + -0.29f * len;             // (float)((1/4 - 0.04) - 0.5)
-    const float clp = lo_rcp(lob);
+    const EasuLobe lobe = easu_analyse(b.w, c.w, e.w, f.w, g.w, h.w, i.w, j.w, k.w, l.w, n.w, o.w, ppx, ppy);
     float3 ac = make_float3(0.0f, 0.0f, 0.0f);
     float aw = 0.0f;
-    easu_tap(ac, aw, 0.0f, -1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, b);
-    easu_tap(ac, aw, 1.0f, -1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, c);
-    easu_tap(ac, aw, -1.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, i);
-    easu_tap(ac, aw, 0.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, j);
-    easu_tap(ac, aw, 0.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, f);
-    easu_tap(ac, aw, -1.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, e);
-    easu_tap(ac, aw, 1.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, k);
-    easu_tap(ac, aw, 2.0f, 1.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, l);
-    easu_tap(ac, aw, 2.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, h);
-    easu_tap(ac, aw, 1.0f, 0.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, g);
-    easu_tap(ac, aw, 1.0f, 2.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, o);
-    easu_tap(ac, aw, 0.0f, 2.0f, ppx, ppy, dirx, diry, len2x, len2y, lob, clp, n);
+    easu_tap(ac, aw, 0.0f, -1.0f, ppx, ppy, lobe, b);
+    easu_tap(ac, aw, 1.0f, -1.0f, ppx, ppy, lobe, c);
+    easu_tap(ac, aw, -1.0f, 1.0f, ppx, ppy, lobe, i);
+    easu_tap(ac, aw, 0.0f, 1.0f, ppx, ppy, lobe, j);
+    easu_tap(ac, aw, 0.0f, 0.0f, ppx, ppy, lobe, f);
+    easu_tap(ac, aw, -1.0f, 0.0f, ppx, ppy, lobe, e);
+    easu_tap(ac, aw, 1.0f, 1.0f, ppx, ppy, lobe, k);
+    easu_tap(ac, aw, 2.0f, 1.0f, ppx, ppy, lobe, l);
+    easu_tap(ac, aw, 2.0f, 0.0f, ppx, ppy, lobe, h);
+    easu_tap(ac, aw, 1.0f, 0.0f, ppx, ppy, lobe, g);
+    easu_tap(ac, aw, 1.0f, 2.0f, ppx, ppy, lobe, o);
+    easu_tap(ac, aw, 0.0f, 2.0f, ppx, ppy, lobe, n);
     const float inv = 1.0f / aw;                       // correctly rounded (ARcpF1 on OpenGL)
     const float mnr = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.x, g.x), j.x), k.x);
     const float mng = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.y, g.y), j.y), k.y);
@@ -147,8 +84,6 @@ __device__ __forceinline__ float3 easu(const float4 (&t)[4][4], float ppx, float
     return make_float3(__builtin_fminf(mxr, __builtin_fmaxf(mnr, ac.x * inv)), __builtin_fminf(mxg, __builtin_fmaxf(mng, ac.y * inv)),
                        __builtin_fminf(mxb, __builtin_fmaxf(mnb, ac.z * inv)));
 }
-
-__device__ __forceinline__ uint32_t to_byte(float v) { return (uint32_t)rintf(v * 255.0f); }
 
 template <int C>
 __device__ __forceinline__ void store_pixel(const EasuArgs& a, int x, int y, float3 pix)
@@ -165,8 +100,6 @@ __device__ __forceinline__ void store_pixel(const EasuArgs& a, int x, int y, flo
     p[a.bi] = (uint8_t)b;
     if (C == 4) p[3] = 255;
 }
-
-__device__ __forceinline__ float pp_of(int ip, float scale, float bias) { return (float)ip * scale + bias; }
 
 template <int C, bool kStaged>
 __global__ __launch_bounds__(256)
@@ -244,19 +177,6 @@ void k_fsr_easu(EasuArgs a)
         }
         if (kStaged) __syncthreads();                               // the stage is reused by the next row of tiles
     }
-}
-
-// The largest fp span (last - first + 1) of any kTile-sized run of outputs 0 .. n - 1, with the kernel's float32 arithmetic.
-int max_fp_span(int n, int tile, float scale, float bias)
-{
-    int worst = 0;
-    for (int i0 = 0; i0 < n; i0 += tile)
-    {
-        const int i1 = std::min(i0 + tile, n) - 1;
-        const int f0 = (int)std::floor((float)i0 * scale + bias), f1 = (int)std::floor((float)i1 * scale + bias);
-        worst = std::max(worst, f1 - f0 + 1);
-    }
-    return worst;
 }
 
 // cvRound of a float32 (round half to even), saturating far beyond the output cap

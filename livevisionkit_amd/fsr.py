@@ -1,12 +1,13 @@
 """FSR 1 EASU scaling (the OBS plugin's FSR filter: FSRFilter / FSREffect, FidelityFX FsrEasuF) over the C-ABI.
 
 Frames are torch uint8 tensors [rows, cols, 3 | 4] on the GPU with contiguous rows (any row pitch: stride(1) == channels, stride(2) == 1).
-apply() works out of place on the context's stream; specification: tests/np_fsr.py and DESIGN.md section 16."""
+apply() works out of place on the context's stream; specification: tests/np_fsr.py and DESIGN.md section 16.  apply() also takes GRAY frames
+[rows, cols] (lvk_hip_fsr_easu_gray)."""
 import ctypes
 import math
 
 from . import _native
-from .stabilization import CHANNELS, FORMAT_BGR, frame_args, out_frame
+from .stabilization import CHANNELS, FORMAT_BGR, FORMAT_GRAY, frame_args, gray_frame_args, out_frame
 
 _c = ctypes
 MAX_CROP = 4096
@@ -61,11 +62,16 @@ class FSRFilter:
 
     def apply(self, frame, fmt=FORMAT_BGR, out=None):
         """Scales `frame` into `out` (a new tensor of the output size when None; it must not overlap `frame`) and returns it.  When the
-        geometry skips, `frame` itself is returned (or copied into `out`)."""
-        ch = CHANNELS.get(fmt)
-        if ch not in (3, 4):
+        geometry skips, `frame` itself is returned (or copied into `out`).  The tensor selects the entry: [rows, cols] is a GRAY frame (`fmt` left
+        at its default or FORMAT_GRAY) and `out` is two-dimensional, [rows, cols, 3 | 4] a frame of format `fmt`."""
+        gray = frame.dim() == 2
+        ch = 1 if gray else CHANNELS.get(fmt)
+        if gray and fmt not in (FORMAT_BGR, FORMAT_GRAY):
+            raise ValueError("a [rows, cols] frame is a GRAY frame")
+        if not gray and ch not in (3, 4):
             raise ValueError("FSR takes BGR / RGB / YUV and BGRA / RGBA frames")
-        src, src_step = frame_args(frame, ch)
+        args = gray_frame_args if gray else (lambda t: frame_args(t, ch))
+        src, src_step = args(frame)
         rows, cols = frame.shape[0], frame.shape[1]
         region, (oh, ow), skip = self.geometry(rows, cols)
         if skip:
@@ -75,8 +81,13 @@ class FSRFilter:
                 raise ValueError("out must have the shape of the frame")
             out.copy_(frame)
             return out
-        out = out_frame(out, frame, (oh, ow, ch), "out must have the output shape %r" % ((oh, ow, ch),))
-        dst, dst_step = frame_args(out, ch)
-        self.ctx._check(self.lib.lvk_hip_fsr_easu(self.ctx.handle, src, src_step, rows, cols, int(fmt), (_c.c_int * 4)(*region), dst, dst_step,
-                                                  oh, ow))
+        shape = (oh, ow) if gray else (oh, ow, ch)
+        out = out_frame(out, frame, shape, "out must have the output shape %r" % (shape,))
+        dst, dst_step = args(out)
+        reg = (_c.c_int * 4)(*region)
+        if gray:
+            rc = self.lib.lvk_hip_fsr_easu_gray(self.ctx.handle, src, src_step, rows, cols, reg, dst, dst_step, oh, ow)
+        else:
+            rc = self.lib.lvk_hip_fsr_easu(self.ctx.handle, src, src_step, rows, cols, int(fmt), reg, dst, dst_step, oh, ow)
+        self.ctx._check(rc)
         return out

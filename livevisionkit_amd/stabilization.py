@@ -24,6 +24,13 @@ def frame_args(frame, channels, kind="uint8"):
     return frame.data_ptr(), frame.stride(0)
 
 
+def gray_frame_args(frame):
+    """(data pointer, row pitch) of a GRAY frame [rows, cols] with contiguous rows (any row pitch)."""
+    if frame.dim() != 2 or frame.stride(1) != 1 or frame.dtype.itemsize != 1:
+        raise ValueError("a packed 8UC1 frame [rows, cols] with contiguous rows is required")
+    return frame.data_ptr(), frame.stride(0)
+
+
 def out_frame(out, frame, shape, message):
     """The destination of an out-of-place filter: a new uint8 tensor of `shape` on `frame`'s device when `out` is None, else `out`
     (ValueError(message) unless it has `shape`)."""
