@@ -770,6 +770,17 @@ int lvk_hip_pyrlk(lvk_hip_ctx* ctx, const void* d_prev, int prev_step, const voi
 int lvk_hip_estimate_global_motion(lvk_hip_ctx* ctx, const float* pts1, const float* pts2, int n, double threshold,
                                    double region_w, double region_h, int full_homography, double H[9], uint8_t* mask);
 
+/* The same estimate with the mode of its local optimisation chosen by the caller, and what the kernel reports of it.
+ *   lo_mode 0   what lvk_hip_estimate_global_motion, the chain and the filter run: the refit rounds stop at a mask fixed point -- after an
+ *               accepted round whose inlier mask equals the mask its refit was computed on, the next round would repeat it bit for bit
+ *               and change nothing.
+ *   lo_mode 1   every round the loop of the specification runs.  Same H, mask and return value, by construction.
+ * lo_info[0] = refit rounds executed, lo_info[1] = 1 when the loop was left at a fixed point with a round still to go (0 in mode 1, and 0, 0
+ * where no kernel ran).  Synchronous; a test entry. */
+int lvk_hip_estimate_global_motion_lo(lvk_hip_ctx* ctx, const float* pts1, const float* pts2, int n, double threshold,
+                                      double region_w, double region_h, int full_homography, int lo_mode, double H[9], uint8_t* mask,
+                                      int lo_info[2]);
+
 /* fast_filter (Functions/Container.tpp:97-121; call site Vision/FrameTracker.cpp:149) as the GPU runs it between the optical
  * flow and the motion estimate: keeps the pairs whose status is non-zero, in the order the reference's back-to-front swap-erase
  * leaves them.  Host arrays (n x 2 floats, n bytes); returns the number of pairs kept (>= 0) or LVK_HIP_ERR_*. */

@@ -110,6 +110,9 @@ _SIG = {
     "lvk_hip_obs_frame_format": (_c.c_int, [_c.c_int]),
     "lvk_hip_estimate_global_motion": (_c.c_int, [_P, _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _c.c_int, _c.c_double,
                                                   _c.c_double, _c.c_double, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint8)]),
+    "lvk_hip_estimate_global_motion_lo": (_c.c_int, [_P, _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _c.c_int, _c.c_double,
+                                                     _c.c_double, _c.c_double, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint8),
+                                                     _c.POINTER(_c.c_int)]),
     "lvk_hip_track_chain": (_c.c_int, [_P, _P, _P]),
     "lvk_stab_default_settings": (None, [_P]),
     "lvk_hip_stab_create": (_c.c_int, [_P, _P, _c.POINTER(_P)]),

@@ -313,6 +313,20 @@ class Context:
             self._check(rc)
         return rc, H.reshape(3, 3), mask
 
+    def estimate_global_motion_lo(self, p1, p2, threshold, lo_mode, region=(480, 270), full_homography=True):
+        """estimate_global_motion with the local optimisation's mode chosen (0: stop at a mask fixed point, the product; 1: every round of the
+        specification's loop); returns (n_inliers, H, mask, refit rounds run, left at a fixed point)."""
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2); p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        H = np.zeros(9, np.float64); mask = np.zeros(len(p1), np.uint8); info = (ctypes.c_int * 2)(-1, -1)
+        rc = self.lib.lvk_hip_estimate_global_motion_lo(self.handle, p1.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                        p2.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(p1), float(threshold),
+                                                        float(region[0]), float(region[1]), 1 if full_homography else 0, int(lo_mode),
+                                                        H.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                        mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), info)
+        if rc in (-1, -2, -3):
+            self._check(rc)
+        return rc, H.reshape(3, 3), mask, info[0], info[1]
+
     # ---- YUV420 <-> packed 444 (SURVEY section 8f row 2) ----------------------------------------------------------
     def ingest_yuv420(self, y, u, v=None, out=None):
         """I420 (y, u, v) or NV12 (y, uv[r/2, c/2, 2]) torch uint8 planes -> packed [rows, cols, 3]."""

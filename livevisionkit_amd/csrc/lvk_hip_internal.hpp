@@ -268,7 +268,8 @@ size_t lvk_ransac_workspace_bytes(int n);
 int lvk_launch_ransac(lvk_hip_ctx* ctx, const float2* d_p1, const float2* d_p2, int n, double threshold, double region_w, double region_h,
                       bool full_homography, void* d_ws, double* d_H, int* d_ninl, uint8_t* d_mask, const int* d_n = nullptr,
                       const int* d_full = nullptr,       // d_full: the model choice lives on the device (full_homography ignored)
-                      LvkHostSignal done = LvkHostSignal{nullptr, 0});
+                      LvkHostSignal done = LvkHostSignal{nullptr, 0},
+                      int lo_mode = 0);                  // 0: the local optimisation stops at a mask fixed point (the product); 1: every round of the specification's loop (diagnostics)
 // fast_filter (Functions/Container.tpp:97-121) of the optical-flow result on the GPU: compacts (prev, matched) by `status` into
 // (d_p1, d_p2) in exactly the order the host's back-to-front swap-erase produces, writes the count to d_count, and mirrors the raw
 // matched points / status flags into device-visible host memory for the host's own bookkeeping.

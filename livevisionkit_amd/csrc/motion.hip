@@ -26,6 +26,7 @@ constexpr int NT = 256;              // threads per block of k_ransac_hypotheses
 constexpr int FT = LVK_FINALIZE_THREADS;
 static_assert(FT == 256 || FT == 512, "4 or 8 waves");
 constexpr int LDS_POINTS = 2048;     // point pairs staged in LDS (16 B each); larger sets are read from global memory
+constexpr int MAX_PAIRS = 1 << 22;   // what score_model's packed (score, count) word holds; the launchers refuse more
 
 // threadIdx.x through an opaque move.  The local-optimisation rounds of k_ransac_finalize are one loop around ~7 000 inlined instructions; what
 // the compiler can derive from the thread index alone (lane predicates, LDS addresses per slot, permute addresses, per-lane selects of the
@@ -161,16 +162,26 @@ __device__ __forceinline__ long long wave_sum_ll(long long v)
 }
 
 // Exact integer sum over the whole block of BT threads (order free).  scratch: BT / 64 int64 in LDS.
+// any != nullptr: also the OR of every thread's `flag`, block-uniform, at no barrier and no LDS word of its own -- a wave's OR is one
+// ballot and rides in bit 63 of the wave's word.  Precondition of that form: every v is non-negative and the block's sum stays below 2^63
+// (score_model, its one caller, asserts it of its packing).
 template <int BT>
-__device__ __forceinline__ long long block_sum_ll(long long v, long long* scratch)
+__device__ __forceinline__ long long block_sum_ll(long long v, long long* scratch, bool flag = false, bool* any = nullptr)
 {
     v = wave_sum_ll(v);
+    if (any) v |= (long long)(__ballot(flag) != 0) << 63;
     __syncthreads();
     if ((tid_now() & 63) == 0) scratch[tid_now() >> 6] = v;
     __syncthreads();
-    long long t = 0;
+    long long t = 0; bool f = false;
 #pragma unroll
-    for (int w = 0; w < BT / 64; w++) t += scratch[w];
+    for (int w = 0; w < BT / 64; w++)
+    {
+        const long long word = scratch[w];
+        t += any ? word & 0x7fffffffffffffffll : word;
+        f = f || word < 0;
+    }
+    if (any) *any = f;
     return t;
 }
 
@@ -182,21 +193,27 @@ __device__ __forceinline__ double wave_sum_f64(double v)          // xor butterf
 }
 
 // Scores model H over all pairs with the whole wave; optionally writes the inlier mask. Returns (score, #inliers) on every lane.
+// ref / differs (both or neither): *differs = the mask written is not byte for byte the mask `ref` (another buffer, written by an earlier
+// pass of this block with the same BT: every thread meets its own bytes again), block-uniform.
 template <int BT>
 __device__ long long score_model(const double* H, const float2* __restrict__ p1, const float2* __restrict__ p2, int n, double t2,
-                                 uint8_t* mask, int* ninl, long long* scratch)
+                                 uint8_t* mask, int* ninl, long long* scratch, const uint8_t* ref = nullptr, bool* differs = nullptr)
 {
-    long long score = 0; long long cnt = 0;
+    long long score = 0; long long cnt = 0; bool diff = false;
     for (int i = tid_now(); i < n; i += BT)
     {
         const float2 a = p1[i], b = p2[i];
         const double e2 = reproj_err2(H, (double)a.x, (double)a.y, (double)b.x, (double)b.y);
         const bool in = e2 <= t2;
         if (in) { score += (long long)((1.0 - e2 / t2) * 1024.0); cnt++; }
+        if (ref) diff = diff || (ref[i] != 0) != in;
         if (mask) mask[i] = in ? 1 : 0;
     }
-    // one block reduction for both: the score of a pair is below 2^10, so the sum over <= 2^22 pairs stays below bit 40
-    const long long both = block_sum_ll<BT>(score + (cnt << 40), scratch);
+    // one block reduction for both: the score of a pair is at most 2^10, so the sum over <= MAX_PAIRS pairs stays below bit 40, and the
+    // count above it leaves bit 63 to block_sum_ll's flag (the launchers refuse more pairs)
+    static_assert((long long)MAX_PAIRS * 1024 < (1ll << 40) && ((long long)MAX_PAIRS << 40) <= (1ll << 62),
+                  "score below bit 40; score + (count << 40) < 2^63: non-negative, bit 63 clear");
+    const long long both = block_sum_ll<BT>(score + (cnt << 40), scratch, diff, differs);
     if (ninl) *ninl = (int)(both >> 40);
     return both & ((1ll << 40) - 1);
 }
@@ -674,13 +691,19 @@ __device__ __forceinline__ void signal_host(LvkHostSignal done)
 // The block has to fit NEXT TO the co-scheduled remap of the overlap mode (4 waves x 80 VGPRs per SIMD leave 192 of a SIMD's 512): as 4
 // waves (one per SIMD) it may take 168 VGPRs, as 8 waves (two per SIMD) 96 each; the unconstrained allocation of 250 made it wait for remap
 // workgroups to retire.
+//
+// The local optimisation stops at a mask fixed point (lo_mode 0, the product): an accepted round whose mask equals, byte for byte, the mask
+// its refit read would be followed by a round that sums the same pairs in the same order, solves the same system and scores the same H --
+// s == best_score, the break that changes nothing.  That round is left out; lo_mode 1 runs it, as the specification's loop is written.
+// lo_info[0] = refits run, lo_info[1] = 1 when the loop was left at a fixed point with a round still to go.
 template <bool STAGED>
 __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(FT == 512 ? 5 : 3)))
 void k_ransac_finalize(const float2* __restrict__ g1, const float2* __restrict__ g2, int n, const int* __restrict__ n_dev, double t2, int full,
                        const int* __restrict__ full_dev, double cx, double cy, double sc,
                        const double* __restrict__ hyp_H, const long long* __restrict__ hyp_score,
                        uint8_t* __restrict__ gmask_a, uint8_t* __restrict__ gmask_b,
-                       double* __restrict__ out_H, int* __restrict__ out_ninl, uint8_t* __restrict__ out_mask, LvkHostSignal done)
+                       double* __restrict__ out_H, int* __restrict__ out_ninl, uint8_t* __restrict__ out_mask, LvkHostSignal done,
+                       int lo_mode, int* __restrict__ lo_info)
 {
     LVK_TL(1);
     LVK_TRACKER_PRIORITY();
@@ -733,7 +756,7 @@ void k_ransac_finalize(const float2* __restrict__ g1, const float2* __restrict__
     if (best_h < 0 || best < 0)
     {
         for (int i = lane; i < n; i += FT) out_mask[i] = 0;
-        if (lane == 0) { for (int q = 0; q < 9; q++) out_H[q] = (q % 4 == 0) ? 1.0 : 0.0; *out_ninl = -2; }
+        if (lane == 0) { for (int q = 0; q < 9; q++) out_H[q] = (q % 4 == 0) ? 1.0 : 0.0; *out_ninl = -2; lo_info[0] = 0; lo_info[1] = 0; }
         signal_host(done);
         return;
     }
@@ -746,13 +769,15 @@ void k_ransac_finalize(const float2* __restrict__ g1, const float2* __restrict__
     long long best_score = score_model<FT>(sBest, p1, p2, n, s_par[3], cur, &ninl, s_scratch);
     __syncthreads();
     RT_MARK();
+    int refits = 0, fixed_point = 0;
     for (int round = 0; round < LO_ROUNDS; round++)
     {
         if (ninl < m) break;
+        refits++;
         if (!refit(full != 0, p1, p2, n, cur, s_par, sA, sb, sH)) break;
         RT_MARK();
-        int nt = 0;
-        const long long s = score_model<FT>(sH, p1, p2, n, s_par[3], trial, &nt, s_scratch);
+        int nt = 0; bool moved = true;
+        const long long s = score_model<FT>(sH, p1, p2, n, s_par[3], trial, &nt, s_scratch, cur, &moved);
         __syncthreads();
         RT_MARK();
         if (s <= best_score) break;
@@ -760,10 +785,12 @@ void k_ransac_finalize(const float2* __restrict__ g1, const float2* __restrict__
         if (lane < 9) sBest[lane] = sH[lane];
         uint8_t* t = cur; cur = trial; trial = t;
         __syncthreads();
+        // (block-uniform: every thread read the same words in score_model.  After the last round there is nothing to leave out.)
+        if (!moved && lo_mode == 0 && round + 1 < LO_ROUNDS) { fixed_point = 1; break; }
     }
     for (int i = lane; i < n; i += FT) out_mask[i] = cur[i];
     if (lane < 9) out_H[lane] = sBest[lane];
-    if (lane == 0) *out_ninl = ninl;
+    if (lane == 0) { *out_ninl = ninl; lo_info[0] = refits; lo_info[1] = fixed_point; }
     signal_host(done);
 #ifdef LVK_RANSAC_TIMING
     RT_MARK();
@@ -810,32 +837,45 @@ void k_match_compact(const float2* __restrict__ prev, const float2* __restrict__
 
 size_t lvk_ransac_workspace_bytes(int n)
 {
-    // hypotheses (H + score) | mask_a | mask_b
-    return (size_t)K_HYPOTHESES * (9 * sizeof(double) + sizeof(long long)) + 2 * (((size_t)n + 255) & ~(size_t)255);
+    // hypotheses (H + score) | mask_a | mask_b | lo_info (refits run, left at a fixed point)
+    return (size_t)K_HYPOTHESES * (9 * sizeof(double) + sizeof(long long)) + 2 * (((size_t)n + 255) & ~(size_t)255) + 2 * sizeof(int);
 }
+
+namespace {
+
+struct RansacWorkspace
+{
+    double* hyp_H; long long* hyp_score; uint8_t* mask_a; uint8_t* mask_b; int* lo_info;
+    RansacWorkspace(void* d_ws, int n)
+    {
+        const size_t mask_bytes = ((size_t)n + 255) & ~(size_t)255;
+        hyp_H = (double*)d_ws; hyp_score = (long long*)(hyp_H + K_HYPOTHESES * 9);
+        mask_a = (uint8_t*)(hyp_score + K_HYPOTHESES); mask_b = mask_a + mask_bytes; lo_info = (int*)(mask_b + mask_bytes);
+    }
+};
+
+} // namespace
 
 // d_p1/d_p2: n pairs; d_ws: lvk_ransac_workspace_bytes(n); outputs d_H (9 doubles), d_ninl, d_mask (n bytes).
 int lvk_launch_ransac(lvk_hip_ctx* ctx, const float2* d_p1, const float2* d_p2, int n, double threshold, double region_w, double region_h,
-                      bool full_homography, void* d_ws, double* d_H, int* d_ninl, uint8_t* d_mask, const int* d_n, const int* d_full, LvkHostSignal done)
+                      bool full_homography, void* d_ws, double* d_H, int* d_ninl, uint8_t* d_mask, const int* d_n, const int* d_full, LvkHostSignal done,
+                      int lo_mode)
 {
     CompactArgs ca{}; ca.full_dev = d_full;
-    LVK_HIP_REQUIRE(ctx, d_p1 && d_p2 && d_ws && d_H && d_ninl && d_mask && (d_n || n >= (full_homography ? 4 : 2)));
-    double* hyp_H = (double*)d_ws;
-    long long* hyp_score = (long long*)(hyp_H + K_HYPOTHESES * 9);
-    uint8_t* mask_a = (uint8_t*)(hyp_score + K_HYPOTHESES);
-    uint8_t* mask_b = mask_a + (((size_t)n + 255) & ~(size_t)255);
+    LVK_HIP_REQUIRE(ctx, d_p1 && d_p2 && d_ws && d_H && d_ninl && d_mask && (d_n || n >= (full_homography ? 4 : 2)) && n <= MAX_PAIRS);
+    const RansacWorkspace ws(d_ws, n);
     const double t2 = threshold * threshold;
     if (n <= LDS_POINTS)
     {
-        hipLaunchKernelGGL(k_ransac_hypotheses<true>, dim3(K_HYPOTHESES), dim3(NT), 0, ctx->stream, d_p1, d_p2, n, d_n, t2, full_homography ? 1 : 0, hyp_H, hyp_score, ca);
+        hipLaunchKernelGGL(k_ransac_hypotheses<true>, dim3(K_HYPOTHESES), dim3(NT), 0, ctx->stream, d_p1, d_p2, n, d_n, t2, full_homography ? 1 : 0, ws.hyp_H, ws.hyp_score, ca);
         hipLaunchKernelGGL(k_ransac_finalize<true>, dim3(1), dim3(FT), 0, ctx->stream, d_p1, d_p2, n, d_n, t2, full_homography ? 1 : 0, d_full,
-                           region_w * 0.5, region_h * 0.5, 2.0 / (region_w + region_h), hyp_H, hyp_score, mask_a, mask_b, d_H, d_ninl, d_mask, done);
+                           region_w * 0.5, region_h * 0.5, 2.0 / (region_w + region_h), ws.hyp_H, ws.hyp_score, ws.mask_a, ws.mask_b, d_H, d_ninl, d_mask, done, lo_mode, ws.lo_info);
     }
     else
     {
-        hipLaunchKernelGGL(k_ransac_hypotheses<false>, dim3(K_HYPOTHESES), dim3(NT), 0, ctx->stream, d_p1, d_p2, n, d_n, t2, full_homography ? 1 : 0, hyp_H, hyp_score, ca);
+        hipLaunchKernelGGL(k_ransac_hypotheses<false>, dim3(K_HYPOTHESES), dim3(NT), 0, ctx->stream, d_p1, d_p2, n, d_n, t2, full_homography ? 1 : 0, ws.hyp_H, ws.hyp_score, ca);
         hipLaunchKernelGGL(k_ransac_finalize<false>, dim3(1), dim3(FT), 0, ctx->stream, d_p1, d_p2, n, d_n, t2, full_homography ? 1 : 0, d_full,
-                           region_w * 0.5, region_h * 0.5, 2.0 / (region_w + region_h), hyp_H, hyp_score, mask_a, mask_b, d_H, d_ninl, d_mask, done);
+                           region_w * 0.5, region_h * 0.5, 2.0 / (region_w + region_h), ws.hyp_H, ws.hyp_score, ws.mask_a, ws.mask_b, d_H, d_ninl, d_mask, done, lo_mode, ws.lo_info);
     }
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
@@ -868,30 +908,27 @@ int lvk_launch_compact_ransac(lvk_hip_ctx* ctx, const float2* d_prev, const floa
     static_assert(LVK_COMPACT_RANSAC_MAX % NT == 0 && LVK_COMPACT_RANSAC_MAX <= LDS_POINTS, "the fused variant compacts into its LDS copy");
     LVK_HIP_REQUIRE(ctx, d_prev && d_matched && d_status && d_p1 && d_p2 && d_count && h_count && h_matched && h_status && n > 0 && n <= LVK_COMPACT_RANSAC_MAX);
     LVK_HIP_REQUIRE(ctx, d_ws && d_H && d_ninl && d_mask);
-    double* hyp_H = (double*)d_ws;
-    long long* hyp_score = (long long*)(hyp_H + K_HYPOTHESES * 9);
-    uint8_t* mask_a = (uint8_t*)(hyp_score + K_HYPOTHESES);
-    uint8_t* mask_b = mask_a + (((size_t)n + 255) & ~(size_t)255);
+    const RansacWorkspace ws(d_ws, n);
     const double t2 = threshold * threshold;
     const CompactArgs ca{d_prev, d_matched, d_status, d_und, region_wf, region_hf, d_p1, d_p2, d_count, h_count, h_matched, h_status, d_n_raw, d_full};
     hipLaunchKernelGGL((k_ransac_hypotheses<true, true>), dim3(K_HYPOTHESES), dim3(NT), 0, ctx->stream, (const float2*)nullptr, (const float2*)nullptr, n, (const int*)nullptr,
-                       t2, full_homography ? 1 : 0, hyp_H, hyp_score, ca);
+                       t2, full_homography ? 1 : 0, ws.hyp_H, ws.hyp_score, ca);
     hipLaunchKernelGGL(k_ransac_finalize<true>, dim3(1), dim3(FT), 0, ctx->stream, (const float2*)d_p1, (const float2*)d_p2, n, (const int*)d_count, t2, full_homography ? 1 : 0, d_full,
-                       region_w * 0.5, region_h * 0.5, 2.0 / (region_w + region_h), hyp_H, hyp_score, mask_a, mask_b, d_H, d_ninl, d_mask, done);
+                       region_w * 0.5, region_h * 0.5, 2.0 / (region_w + region_h), ws.hyp_H, ws.hyp_score, ws.mask_a, ws.mask_b, d_H, d_ninl, d_mask, done, 0, ws.lo_info);
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
 }
 
-extern "C" {
+namespace {
 
-// Synchronous test entry point: host point arrays (n x 2 floats), outputs H (9 doubles, row major), mask (n bytes).
-// Returns the inlier count (>= 0) or a negative status: LVK_HIP_ERR_* or -10 - (reason) when no model was found.
-int lvk_hip_estimate_global_motion(lvk_hip_ctx* ctx, const float* pts1, const float* pts2, int n, double threshold,
-                                   double region_w, double region_h, int full_homography, double H[9], uint8_t* mask)
+// Both synchronous test entry points: host point arrays (n x 2 floats), outputs H (9 doubles, row major), mask (n bytes) and, where asked
+// for, the two ints k_ransac_finalize leaves behind its masks.
+int estimate_global_motion(lvk_hip_ctx* ctx, const float* pts1, const float* pts2, int n, double threshold, double region_w, double region_h,
+                           int full_homography, double H[9], uint8_t* mask, int lo_mode, int* lo_info)
 {
-    LVK_HIP_ENTRY(ctx);
     LVK_HIP_REQUIRE(ctx, pts1 && pts2 && H && mask && n >= 0);
     for (int q = 0; q < 9; q++) H[q] = (q % 4 == 0) ? 1.0 : 0.0;
+    if (lo_info) lo_info[0] = lo_info[1] = 0;
     for (int i = 0; i < n; i++) mask[i] = 0;
     if (n < (full_homography ? 4 : 2)) return -11;
     float2 *d_p1 = nullptr, *d_p2 = nullptr; void* d_ws = nullptr; double* d_H = nullptr; int* d_n = nullptr; uint8_t* d_mask = nullptr;
@@ -903,19 +940,43 @@ int lvk_hip_estimate_global_motion(lvk_hip_ctx* ctx, const float* pts1, const fl
         (e = hipMemcpyAsync(d_p1, pts1, n * sizeof(float2), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(d_p2, pts2, n * sizeof(float2), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
     { cleanup(); return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(e)); }
-    int rc = lvk_launch_ransac(ctx, d_p1, d_p2, n, threshold, region_w, region_h, full_homography != 0, d_ws, d_H, d_n, d_mask);
+    int rc = lvk_launch_ransac(ctx, d_p1, d_p2, n, threshold, region_w, region_h, full_homography != 0, d_ws, d_H, d_n, d_mask,
+                               nullptr, nullptr, LvkHostSignal{nullptr, 0}, lo_mode);
     int ninl = 0;
     if (rc == LVK_HIP_OK)
     {
         if ((e = hipMemcpyAsync(H, d_H, 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
             (e = hipMemcpyAsync(&ninl, d_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
             (e = hipMemcpyAsync(mask, d_mask, n, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+            (lo_info && (e = hipMemcpyAsync(lo_info, RansacWorkspace(d_ws, n).lo_info, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) ||
             (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
         { cleanup(); return ctx->fail(LVK_HIP_ERR_RUNTIME, hipGetErrorString(e)); }
     }
     cleanup();
     if (rc != LVK_HIP_OK) return rc;
     return ninl >= 0 ? ninl : -10 + ninl;
+}
+
+} // namespace
+
+extern "C" {
+
+// Returns the inlier count (>= 0) or a negative status: LVK_HIP_ERR_* or -10 - (reason) when no model was found.
+int lvk_hip_estimate_global_motion(lvk_hip_ctx* ctx, const float* pts1, const float* pts2, int n, double threshold,
+                                   double region_w, double region_h, int full_homography, double H[9], uint8_t* mask)
+{
+    LVK_HIP_ENTRY(ctx);
+    return estimate_global_motion(ctx, pts1, pts2, n, threshold, region_w, region_h, full_homography, H, mask, 0, nullptr);
+}
+
+// The same with the local optimisation's mode chosen by the caller (0: the product's, 1: every round of the specification's loop) and what
+// k_ransac_finalize reports of it: lo_info[0] = refits run, lo_info[1] = left at a mask fixed point.
+int lvk_hip_estimate_global_motion_lo(lvk_hip_ctx* ctx, const float* pts1, const float* pts2, int n, double threshold,
+                                      double region_w, double region_h, int full_homography, int lo_mode, double H[9], uint8_t* mask, int lo_info[2])
+{
+    LVK_HIP_ENTRY(ctx);
+    LVK_HIP_REQUIRE(ctx, lo_info && (lo_mode == 0 || lo_mode == 1));
+    return estimate_global_motion(ctx, pts1, pts2, n, threshold, region_w, region_h, full_homography, H, mask, lo_mode, lo_info);
 }
 
 // Synchronous test entry point of the GPU-side fast_filter: host arrays in, compacted pairs + count out.
