@@ -3,7 +3,8 @@
 // ADBFilter.cpp:130-136: apply(frame, frame, true), then draw_influence(frame) in test mode); the filter chains in CompositeFilter and takes the
 // frames FrameIngest::upload_obs_frame makes.  filter() dispatches on the frame's type: 8UC3 (BGR / RGB / YUV), 8UC1 of format GRAY and 8UC4 of format
 // BGRA / RGBA (lvk_hip_deblock_apply_gray / _c4: the reference's calls per channel, alpha included); draw_influence is 8UC3 only, like the reference's,
-// whose overlay is an 8UC3 buffer (DeblockingFilter.cpp:120).  Included by LiveVisionKit.hpp.
+// whose overlay is an 8UC3 buffer (DeblockingFilter.cpp:120).  apply(VideoFrame420, VideoFrame420) takes the plugin's I420 / NV12 planes in one call
+// (lvk_hip_deblock_apply_yuv420, out of place).  Included by LiveVisionKit.hpp.
 #pragma once
 
 #include "LiveVisionKit.hpp"
@@ -45,6 +46,34 @@ public:
             hip::ContextLock lock(m_Ctx->mutex());
             m_Ctx->check(lvk_hip_deblock_configure(m_Handle, &s), "DeblockingFilter::configure");
         }
+    }
+
+    // The OBS asynchronous path in one call: I420 / NV12 planes in, planes out (lvk_hip_deblock_apply_yuv420), byte for byte
+    // upload_obs_frame -> apply(frame, frame) -> download_ocl_frame without the packed frame between them.  Out of place: `output` is created at the
+    // input's size, layout and context; filter_region() and draw_influence (on a packed 8UC3 frame) answer as after the packed apply.
+    using VideoFilter::apply;
+    void apply(const VideoFrame420& input, VideoFrame420& output, const bool profile = false)
+    {
+        LVK_HIP_ASSERT(!input.empty());
+        LVK_HIP_ASSERT(&input != &output);
+        if (!m_Handle)
+        {
+            m_Ctx = input.context();
+            const lvk_deblock_settings s = to_c(m_Settings);
+            hip::ContextLock lock(m_Ctx->mutex());
+            m_Ctx->check(lvk_hip_deblock_create(m_Ctx->get(), &s, &m_Handle), "DeblockingFilter");
+        }
+        sync_gpu(profile); frame_timer().start();
+        output.create({input.cols, input.rows}, input.nv12, input.context());
+        LVK_HIP_ASSERT(output.y() != input.y());
+        output.timestamp = input.timestamp;
+        run(input.context(), [&] {
+            m_Ctx->check(lvk_hip_deblock_apply_yuv420(m_Handle, input.y(), input.y_step(), input.u(), input.uv_step(), input.v(), input.uv_step(),
+                                                      output.y(), output.y_step(), output.u(), output.uv_step(), output.v(), output.uv_step(),
+                                                      input.nv12 ? 1 : 0, input.rows, input.cols, nullptr),
+                         "DeblockingFilter::apply(4:2:0)");
+        });
+        sync_gpu(profile); frame_timer().stop();
     }
 
     void draw_influence(VideoFrame& frame) const                                  // DeblockingFilter.cpp:114-131

@@ -632,6 +632,7 @@ public:
 protected:
     virtual void filter(VideoFrame&& input, VideoFrame& output) { output = std::move(input); }
     virtual void sync_gpu(bool /*trigger*/) {}
+    Stopwatch& frame_timer() { return m_FrameTimer; }      // for a filter's apply overloads on other frame types (4:2:0 planes)
 private:
     Stopwatch m_FrameTimer;
     const std::string m_Alias;
@@ -652,15 +653,17 @@ protected:
 
     void adopt(const VideoFrame& frame) { if (!m_Ctx) m_Ctx = frame.context(); }      // the first frame's context, never replaced
     template <typename F>
-    void run(const VideoFrame& src, F&& launch) const
+    void run(const VideoFrame& src, F&& launch) const { run(src.context(), std::forward<F>(launch)); }
+    template <typename F>
+    void run(const std::shared_ptr<hip::Context>& src, F&& launch) const        // `src`: the context the frame (packed or 4:2:0 planes) lives on
     {
-        const bool foreign = src.context() && src.context() != m_Ctx;
-        if (foreign) m_Ctx->wait_for(*src.context());
+        const bool foreign = src && src != m_Ctx;
+        if (foreign) m_Ctx->wait_for(*src);
         {
             hip::ContextLock lock(m_Ctx->mutex());
             launch();
         }
-        if (foreign) src.context()->wait_for(*m_Ctx);
+        if (foreign) src->wait_for(*m_Ctx);
     }
     void sync_gpu(bool trigger) override { if (trigger && m_Ctx) { hip::ContextLock lock(m_Ctx->mutex()); m_Ctx->check(lvk_hip_sync(m_Ctx->get()), "sync_gpu"); } }
 

@@ -831,6 +831,9 @@ int lvk_hip_track_chain(lvk_hip_ctx* ctx, const lvk_track_chain_desc* desc, lvk_
  * Returns ex * ey, or LVK_HIP_ERR_ARG before the first apply or when capacity < ex * ey. */
 int lvk_hip_deblock_get_grid(lvk_hip_deblock* deb, uint8_t* mean, uint8_t* grid, float* keep_block, int capacity, int extent_xy[2]);
 
+/* The deblocking filter on the planes of an I420 / NV12 frame in one call, lvk_hip_deblock_apply_yuv420 on the same handle, is declared in
+ * lvk_hip_deblock_420.h, which this header includes at its end like lvk_hip_deblock_px.h. */
+
 /* CAS host constant (CasSetup's const1.x, float32, each operation rounded on its own): peak = -(1 / (5 s + ((-8) s + 8))) with
  * s = clamp(sharpness, 0, 1).  Needs no device.  LVK_HIP_ERR_ARG for a NaN sharpness or a NULL peak. */
 int lvk_hip_cas_const(float sharpness, float* peak);
@@ -872,5 +875,6 @@ int lvk_hip_area_resize_path(lvk_hip_ctx* ctx, const void* d_src, int src_step, 
 }
 #endif
 
+#include "lvk_hip_deblock_420.h"  /* lvk_hip_deblock_apply_yuv420 (PART 2) */
 #include "lvk_hip_deblock_px.h"   /* lvk_hip_deblock_apply_gray / _c4 (PART 2) */
 #endif /* LVK_HIP_H */

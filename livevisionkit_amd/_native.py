@@ -179,6 +179,12 @@ _SIG_DEBLOCK_PX = {
     "lvk_hip_deblock_apply_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
 }
 
+# what include/lvk_hip_deblock_420.h declares (lvk_hip.h includes it; its pin: tests/test_deblock_420_spec.py)
+_SIG_DEBLOCK_420 = {
+    "lvk_hip_deblock_apply_yuv420": (_c.c_int, [_P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int,
+                                                _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+}
+
 _lib = None
 
 
@@ -192,6 +198,11 @@ def symbols_deblock_px():
     return sorted(_SIG_DEBLOCK_PX.keys())
 
 
+def symbols_deblock_420():
+    """The names include/lvk_hip_deblock_420.h declares."""
+    return sorted(_SIG_DEBLOCK_420.keys())
+
+
 def load():
     """Load liblvk_hip.so and bind every declared symbol; raises if the library or a symbol is missing."""
     global _lib
@@ -203,7 +214,7 @@ def load():
             "(or `make -C livevisionkit_amd/csrc`). There is no CPU fallback.")
     import torch  # noqa: F401  (loads the process-wide HIP runtime first)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX}.items():
+    for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX, **_SIG_DEBLOCK_420}.items():
         fn = getattr(lib, name)      # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,6 +1,7 @@
 // lvk::DeblockingFilter (Filters/DeblockingFilter.{hpp,cpp}) on the MI355X: the adaptive blend of a median-smoothed frame into the original, in
 // place on a packed frame of one (8UC1, GRAY), three (8UC3, BGR / RGB / YUV) or four (8UC4, BGRA / RGBA) bytes per pixel.
-// Specification: tests/np_deblock.py, tests/np_deblock_px.py and DESIGN.md sections 13 and 23.
+// Specification: tests/np_deblock.py, tests/np_deblock_px.py and DESIGN.md sections 13 and 23.  What this unit shares with deblock_420.hip (the
+// same filter on I420 / NV12 planes) -- the handle, the per-pixel arithmetic, the downscale's body, the geometry -- is in deblock_core.hpp.
 //
 // The reference's filter is made of channel-agnostic OpenCV calls (Filters/DeblockingFilter.cpp:48-110: cv::resize, cv::medianBlur, reformatTo(GRAY),
 // cv::blendLinear), so every pixel size is the reference's own: one operation order and one set of rounding rules, per channel.  The ALPHA byte of a
@@ -30,79 +31,20 @@
 // draw_influence (8UC3 only, as in the reference) is the three-channel blend with a constant colour for `smooth` and the keep_block of the last apply.
 // No load or store touches a byte outside the rw * BPP bytes of a region row, and only the region is written.  Three-channel pixels are moved byte by
 // byte and need no alignment; a four-channel frame is dword-aligned (apply refuses others).
-#include "lvk_hip_internal.hpp"
+#include "deblock_core.hpp"
 
-#include <cmath>
-#include <algorithm>
-#include <vector>
-
-int lvk_get_lin8tab(lvk_hip_ctx* ctx, int ssize, int dsize, bool vertical, const Lin8Entry** d_out);   // ingest.hip
-
-struct lvk_hip_deblock
-{
-    lvk_hip_ctx* ctx = nullptr;
-    lvk_deblock_settings settings{};
-    // geometry of the last apply (draw_influence reuses its maps)
-    int rh = 0, rw = 0, ey = 0, ex = 0, hs = 0, ws = 0;
-    bool have_maps = false;
-    // device buffers, sized in bytes for the geometry and pixel size they were last allocated for (lvk_hip_malloc pool of the context)
-    uint8_t* d_small = nullptr; uint8_t* d_median = nullptr; size_t small_cap = 0, median_cap = 0;
-    uint8_t* d_grid = nullptr; float* d_keep = nullptr; size_t grid_cap = 0, keep_cap = 0;       // d_grid: mean (cells) | grid (cells)
-    // area tables of the non-integer downscale, keyed by (rh, rw, hs, ws, scale)
-    int2* d_range = nullptr; AreaTabEntry* d_tab = nullptr; size_t range_cap = 0, tab_cap = 0;
-    int2* d_xr = nullptr; int2* d_yr = nullptr; AreaTabEntry* d_xt = nullptr; AreaTabEntry* d_yt = nullptr;
-    int tab_rh = -1, tab_rw = -1, tab_hs = -1, tab_ws = -1; double tab_scale = 0.0;
-
-    void release()
-    {
-        lvk_hip_free(ctx, d_small); lvk_hip_free(ctx, d_median); lvk_hip_free(ctx, d_grid); lvk_hip_free(ctx, d_keep);
-        lvk_hip_free(ctx, d_range); lvk_hip_free(ctx, d_tab);
-        d_small = d_median = d_grid = nullptr; d_keep = nullptr; d_range = nullptr; d_tab = nullptr;
-        small_cap = median_cap = grid_cap = keep_cap = range_cap = tab_cap = 0;
-    }
-};
+using namespace deblock;
 
 namespace {
 
-constexpr int kMaxFilterSize = 255;       // apply refuses larger windows (declared deviation)
 constexpr int kMedTile = 16;              // median: 16 x 16 outputs per block
 constexpr int kMedLdsMaxK = 113;          // (16 + k - 1)^2 packed pixels fit 64 KiB of LDS up to this k; larger k read global memory
-
-__device__ __forceinline__ int sat_u8(float v)           // saturate_cast<uchar>(float): round half to even, clamp
-{
-    const float r = rintf(v);
-    return r < 0.f ? 0 : r > 255.f ? 255 : (int)r;
-}
 
 __device__ __forceinline__ long long wave_sum(long long v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// resizeAreaFast_ of one block of bs x bs values: 2 x 2 as (sum + 2) >> 2, else sum * (1.f / area) rounded half to even
-__device__ __forceinline__ int box_mean(long long sum, int bs, float inv_area)
-{
-    return bs == 2 ? (int)((sum + 2) >> 2) : sat_u8((float)sum * inv_area);
-}
-
-__device__ __forceinline__ int byte_of(uint32_t v, int c) { return (int)((v >> (8 * c)) & 255u); }
-
-template <int BPP>
-__device__ __forceinline__ uint32_t load_pixel(const uint8_t* __restrict__ p)       // a pixel's channels in bytes 0 .. BPP - 1
-{
-    if constexpr (BPP == 4) return *reinterpret_cast<const uint32_t*>(p);
-    else if constexpr (BPP == 3) return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-    else return *p;
-}
-
-template <int BPP>
-__device__ __forceinline__ void store_pixel(uint8_t* __restrict__ p, uint32_t v)
-{
-    if constexpr (BPP == 4) *reinterpret_cast<uint32_t*>(p) = v;
-    else if constexpr (BPP == 3) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); }
-    else *p = (uint8_t)v;
 }
 
 // The grey of the block statistics.  GRAY: the byte itself.  Else RGB2Gray<uchar> of the colour bytes; blue_shift: the bit position of the blue
@@ -163,9 +105,7 @@ void k_deblock_stats(const uint8_t* __restrict__ frame, int step, int blue_shift
     }
 }
 
-// INTER_AREA of the region (BPP channels) to hs x ws.  iscale > 0: integer scale (resizeAreaFast_; cells that reach past the source -- a destination
-// size rounded up -- average what they cover, (float)sum / count); iscale == 0: separable area tables, float accumulation in table order (per source
-// row the x taps, then the rows weighted by their beta).
+// INTER_AREA of the region (BPP channels) to hs x ws, one thread per output pixel: down_pixel of deblock_core.hpp on the packed frame's pixels
 template <int BPP>
 __global__ __launch_bounds__(256)
 void k_deblock_down(const uint8_t* __restrict__ src, int step, int rh, int rw, uint8_t* __restrict__ dst, int hs, int ws,
@@ -175,50 +115,8 @@ void k_deblock_down(const uint8_t* __restrict__ src, int step, int rh, int rw, u
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (x >= ws || y >= hs) return;
     uint8_t* d = dst + ((size_t)y * ws + x) * BPP;
-    uint32_t out = 0;
-    if (iscale > 0)
-    {
-        const int x0 = x * iscale, y0 = y * iscale;
-        const int x1 = min(x0 + iscale, rw), y1 = min(y0 + iscale, rh);
-        const bool full = x0 + iscale <= rw && y0 + iscale <= rh;
-        int s[BPP] = {};
-        for (int yy = y0; yy < y1; yy++)
-        {
-            const uint8_t* r = src + (size_t)yy * step;
-            for (int xx = x0; xx < x1; xx++)
-            {
-                const uint32_t v = load_pixel<BPP>(r + (size_t)xx * BPP);
-#pragma unroll
-                for (int c = 0; c < BPP; c++) s[c] += byte_of(v, c);
-            }
-        }
-        const float cnt = (float)((x1 - x0) * (y1 - y0));
-#pragma unroll
-        for (int c = 0; c < BPP; c++)
-            out |= (uint32_t)(full ? box_mean(s[c], iscale, inv_area) : sat_u8((float)s[c] / cnt)) << (8 * c);
-        store_pixel<BPP>(d, out);
-        return;
-    }
-    const int2 rx = xr[x], ry = yr[y];
-    float a[BPP] = {};
-    for (int j = 0; j < ry.y; j++)
-    {
-        const AreaTabEntry ty = yt[ry.x + j];
-        const uint8_t* r = src + (size_t)ty.si * step;
-        float b[BPP] = {};
-        for (int i = 0; i < rx.y; i++)
-        {
-            const AreaTabEntry tx = xt[rx.x + i];
-            const uint32_t v = load_pixel<BPP>(r + (size_t)tx.si * BPP);
-#pragma unroll
-            for (int c = 0; c < BPP; c++) b[c] = b[c] + (float)byte_of(v, c) * tx.alpha;
-        }
-#pragma unroll
-        for (int c = 0; c < BPP; c++) a[c] = a[c] + ty.alpha * b[c];
-    }
-#pragma unroll
-    for (int c = 0; c < BPP; c++) out |= (uint32_t)sat_u8(a[c]) << (8 * c);
-    store_pixel<BPP>(d, out);
+    down_pixel<BPP>([&](int yy) { return src + (size_t)yy * step; }, [](const uint8_t* r, int xx) { return load_pixel<BPP>(r + (size_t)xx * BPP); },
+                    d, x, y, rh, rw, iscale, inv_area, xr, xt, yr, yt);
 }
 
 template <int BPP>
@@ -310,28 +208,6 @@ void k_deblock_median(const uint8_t* __restrict__ src, int rows, int cols, uint8
     store_pixel<BPP>(dst + ((size_t)y * cols + x) * BPP, m);
 }
 
-// `keep` of one pixel: the float bilinear of keep_block (k0 / k1: its two rows)
-__device__ __forceinline__ float keep_at(const float* __restrict__ k0, const float* __restrict__ k1, const LinTabEntry& tx, const LinTabEntry& ty)
-{
-    const float h0 = k0[tx.s0] * tx.a0 + k0[tx.s1] * tx.a1;
-    const float h1 = k1[tx.s0] * tx.a0 + k1[tx.s1] * tx.a1;
-    return h0 * ty.a0 + h1 * ty.a1;
-}
-
-// the 8U bilinear of one channel from its four taps (11-bit coefficients, cv::resize INTER_LINEAR on 8U)
-__device__ __forceinline__ int lin8(int p00, int p01, int p10, int p11, const Lin8Entry& tx, int b0, int b1)
-{
-    const int h0 = p00 * tx.a0 + p01 * tx.a1;
-    const int h1 = p10 * tx.a0 + p11 * tx.a1;
-    return ((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 0xff;
-}
-
-// saturate_cast<uchar>((src * keep + smooth * deblock) / (keep + deblock + 1e-5f)); every product / sum is its own rounding (-ffp-contract=off)
-__device__ __forceinline__ int blend_px(int c, int s, float keep, float deb, float den)
-{
-    return sat_u8(((float)c * keep + (float)s * deb) / den);
-}
-
 // In place on the region, three and four channels: one thread per pixel.  INFLUENCE: `smooth` is the constant `colour` (draw_influence).
 // One loop over the channels, each its `smooth` and then its blend: with all of `smooth` packed first the divisions queue behind every tap, which
 // measured 0.4 % slower per four-channel apply at 4K.
@@ -416,66 +292,26 @@ void k_deblock_blend_gray(uint8_t* __restrict__ frame, int step, int rh, int rw,
     }
 }
 
-// computeResizeAreaTab for a scale given by the caller (the 1 / filter_scaling downscale: scale = 1 / (double)(1.f / s), not ssize / dsize)
-void area_tab(int ssize, int dsize, double scale, std::vector<int2>& range, std::vector<AreaTabEntry>& tab)
-{
-    range.assign((size_t)dsize, int2{0, 0});
-    tab.clear();
-    for (int dx = 0; dx < dsize; dx++)
-    {
-        const double fsx1 = dx * scale, fsx2 = fsx1 + scale;
-        const double cell = std::min(scale, ssize - fsx1);
-        int sx1 = (int)std::ceil(fsx1), sx2 = (int)std::floor(fsx2);
-        sx2 = std::min(sx2, ssize - 1);
-        sx1 = std::min(sx1, sx2);
-        const int start = (int)tab.size();
-        if (sx1 - fsx1 > 1e-3) tab.push_back({sx1 - 1, (float)((sx1 - fsx1) / cell)});
-        for (int sx = sx1; sx < sx2; sx++) tab.push_back({sx, (float)(1.0 / cell)});
-        if (fsx2 - sx2 > 1e-3) tab.push_back({sx2, (float)(std::min(std::min(fsx2 - sx2, 1.0), cell) / cell)});
-        range[(size_t)dx] = int2{start, (int)tab.size() - start};
-    }
-}
-
-int small_extent(int n, float scaling)          // saturate_cast<int>(n * (double)(1.f / s)); 0 where it does not fit an int
-{
-    const double v = std::rint((double)n * (double)(1.0f / scaling));
-    return v >= 1.0 && v <= 2147483647.0 ? (int)v : 0;
-}
-
-int ensure(lvk_hip_ctx* ctx, void** p, size_t& cap, size_t bytes)
-{
-    if (*p && cap >= bytes) return LVK_HIP_OK;
-    if (*p) { lvk_hip_free(ctx, *p); *p = nullptr; cap = 0; }
-    const int rc = lvk_hip_malloc(ctx, bytes, p);
-    if (rc == LVK_HIP_OK) cap = bytes;
-    return rc;
-}
-
-int upload_area_tabs(lvk_hip_deblock* d, int rh, int rw, int hs, int ws, double scale)
-{
-    if (d->d_range && d->tab_rh == rh && d->tab_rw == rw && d->tab_hs == hs && d->tab_ws == ws && d->tab_scale == scale) return LVK_HIP_OK;
-    std::vector<int2> xr, yr; std::vector<AreaTabEntry> xt, yt;
-    area_tab(rw, ws, scale, xr, xt);
-    area_tab(rh, hs, scale, yr, yt);
-    // one block: x ranges | y ranges, and one: x taps | y taps (each range indexes its own axis' taps)
-    std::vector<int2> ranges(xr); ranges.insert(ranges.end(), yr.begin(), yr.end());
-    std::vector<AreaTabEntry> taps(xt); taps.insert(taps.end(), yt.begin(), yt.end());
-    int rc;
-    if ((rc = ensure(d->ctx, (void**)&d->d_range, d->range_cap, ranges.size() * sizeof(int2))) != LVK_HIP_OK) return rc;
-    if ((rc = ensure(d->ctx, (void**)&d->d_tab, d->tab_cap, std::max<size_t>(taps.size(), 1) * sizeof(AreaTabEntry))) != LVK_HIP_OK) return rc;
-    // (synchronous, once per geometry -- like the context's INTER_LINEAR / INTER_AREA table caches; the host vectors die with this call)
-    LVK_HIP_CHECK(d->ctx, hipStreamSynchronize(d->ctx->stream));
-    LVK_HIP_CHECK(d->ctx, hipMemcpy(d->d_range, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice));
-    if (!taps.empty()) LVK_HIP_CHECK(d->ctx, hipMemcpy(d->d_tab, taps.data(), taps.size() * sizeof(AreaTabEntry), hipMemcpyHostToDevice));
-    d->d_xr = d->d_range; d->d_yr = d->d_range + xr.size();
-    d->d_xt = d->d_tab; d->d_yt = d->d_tab + xt.size();
-    d->tab_rh = rh; d->tab_rw = rw; d->tab_hs = hs; d->tab_ws = ws; d->tab_scale = scale;
-    return LVK_HIP_OK;
-}
-
 bool settings_valid(const lvk_deblock_settings& s)
 {
     return s.block_size > 0 && s.filter_size >= 3 && s.filter_size % 2 == 1 && s.detection_levels > 0 && s.filter_scaling > 1.0f;
+}
+
+// the block statistics of `frame` (BPP bytes per pixel, its grey by `format`) into the handle's grids
+template <int BPP>
+int launch_stats(lvk_hip_deblock* d, const uint8_t* frame, int step, int format, const Geometry& g)
+{
+    lvk_hip_ctx* ctx = d->ctx;
+    const lvk_deblock_settings& s = d->settings;
+    const size_t cells = (size_t)g.ey * g.ex;
+    const float inv_area_bs = 1.0f / (float)((long long)g.bs * g.bs);
+    const int blue_shift = format == LVK_FORMAT_YUV ? -1 : format == LVK_FORMAT_RGB || format == LVK_FORMAT_RGBA ? 16 : 0;     // gray_of
+    const int dwords = BPP == 1 && g.bs % 4 == 0 && ((uintptr_t)frame & 3u) == 0 && (step & 3) == 0;
+    hipLaunchKernelGGL(k_deblock_stats<BPP>, dim3((g.ex + 3) / 4, g.ey), dim3(256), 0, ctx->stream, frame, step, blue_shift, g.bs, g.ex,
+                       inv_area_bs, (int)std::min<uint32_t>(s.detection_levels, 256u), 1.0 / (double)s.detection_levels, dwords,
+                       d->d_grid, d->d_grid + cells, d->d_keep);
+    LVK_HIP_CHECK(ctx, hipGetLastError());
+    return LVK_HIP_OK;
 }
 
 template <int BPP>
@@ -502,13 +338,7 @@ int launch_blend(lvk_hip_ctx* ctx, uint8_t* frame, int step, const lvk_hip_deblo
     const LinTabEntry *kx, *ky;
     const Lin8Entry *sx = nullptr, *sy = nullptr;
     int rc;
-    if ((rc = lvk_get_lintab(ctx, d->ex, d->rw, false, &kx)) != LVK_HIP_OK) return rc;
-    if ((rc = lvk_get_lintab(ctx, d->ey, d->rh, true, &ky)) != LVK_HIP_OK) return rc;
-    if (!influence)
-    {
-        if ((rc = lvk_get_lin8tab(ctx, d->ws, d->rw, false, &sx)) != LVK_HIP_OK) return rc;
-        if ((rc = lvk_get_lin8tab(ctx, d->hs, d->rh, true, &sy)) != LVK_HIP_OK) return rc;
-    }
+    if ((rc = blend_tables(ctx, d, !influence, &kx, &ky, &sx, &sy)) != LVK_HIP_OK) return rc;
     // GRAY: groups of four pixels; a row that starts 1 .. 3 bytes above a dword boundary spreads over one group more
     const int across = BPP == 1 ? (d->rw + 3) / 4 + 1 : d->rw;
     const dim3 grid((across + 63) / 64, (d->rh + 3) / 4), block(64, 4);
@@ -543,49 +373,38 @@ int apply(lvk_hip_deblock* d, void* d_frame, int step, int rows, int cols, int f
         if (((uintptr_t)d_frame & 3u) || (step & 3))
             return ctx->fail(LVK_HIP_ERR_ARG, name + ": a four-channel frame is 4-byte aligned with a pitch that is a multiple of 4");
     }
-    LVK_HIP_REQUIRE(ctx, s.filter_size <= (uint32_t)kMaxFilterSize);
-    const int bs = s.block_size > (uint32_t)std::max(rows, cols) ? 0 : (int)s.block_size;
-    const int ex = bs ? cols / bs : 0, ey = bs ? rows / bs : 0;
-    if (ex == 0 || ey == 0) return ctx->fail(LVK_HIP_ERR_ARG, name + ": the frame holds no whole macroblock (cv::resize of an empty region)");
-    const int rw = ex * bs, rh = ey * bs;
-    const int ws = small_extent(rw, s.filter_scaling), hs = small_extent(rh, s.filter_scaling);
-    if (ws == 0 || hs == 0) return ctx->fail(LVK_HIP_ERR_ARG, name + ": the 1 / filter_scaling downscale of the region is empty");
-
-    // downscale mode: resizeAreaFast_ when 1 / (double)(1.f / s) is an integer, else the area tables of that scale
-    const double scale = 1.0 / (double)(1.0f / s.filter_scaling);
-    const int iscale = (int)std::lrint(scale);
-    const bool fast = std::fabs(scale - iscale) < 2.220446049250313e-16;
-
+    Geometry g;
     int rc;
-    const size_t sb = (size_t)hs * ws * BPP, cells = (size_t)ey * ex;
-    if ((rc = ensure(ctx, (void**)&d->d_small, d->small_cap, sb)) != LVK_HIP_OK) return rc;
-    if ((rc = ensure(ctx, (void**)&d->d_median, d->median_cap, sb)) != LVK_HIP_OK) return rc;
-    if ((rc = ensure(ctx, (void**)&d->d_grid, d->grid_cap, cells * 2)) != LVK_HIP_OK) return rc;
-    if ((rc = ensure(ctx, (void**)&d->d_keep, d->keep_cap, cells * sizeof(float))) != LVK_HIP_OK) return rc;
-    if (!fast && (rc = upload_area_tabs(d, rh, rw, hs, ws, scale)) != LVK_HIP_OK) return rc;
+    if ((rc = geometry(ctx, s, rows, cols, name, g)) != LVK_HIP_OK) return rc;
+    if ((rc = reserve(d, g, BPP)) != LVK_HIP_OK) return rc;
 
     uint8_t* frame = (uint8_t*)d_frame;
-    const float inv_area_bs = 1.0f / (float)((long long)bs * bs);
-    const int blue_shift = format == LVK_FORMAT_YUV ? -1 : format == LVK_FORMAT_RGB || format == LVK_FORMAT_RGBA ? 16 : 0;     // gray_of
-    const int dwords = BPP == 1 && bs % 4 == 0 && ((uintptr_t)d_frame & 3u) == 0 && (step & 3) == 0;
-    hipLaunchKernelGGL(k_deblock_stats<BPP>, dim3((ex + 3) / 4, ey), dim3(256), 0, ctx->stream, (const uint8_t*)frame, step, blue_shift, bs, ex,
-                       inv_area_bs, (int)std::min<uint32_t>(s.detection_levels, 256u), 1.0 / (double)s.detection_levels, dwords,
-                       d->d_grid, d->d_grid + cells, d->d_keep);
-    LVK_HIP_CHECK(ctx, hipGetLastError());
-    const float inv_area_s = fast ? 1.0f / (float)((long long)iscale * iscale) : 0.0f;
-    hipLaunchKernelGGL(k_deblock_down<BPP>, dim3((ws + 63) / 64, (hs + 3) / 4), dim3(64, 4), 0, ctx->stream, (const uint8_t*)frame, step, rh, rw,
-                       d->d_small, hs, ws, fast ? iscale : 0, inv_area_s, (const int2*)d->d_xr, (const AreaTabEntry*)d->d_xt,
+    if ((rc = launch_stats<BPP>(d, frame, step, format, g)) != LVK_HIP_OK) return rc;
+    const float inv_area_s = g.fast ? 1.0f / (float)((long long)g.iscale * g.iscale) : 0.0f;
+    hipLaunchKernelGGL(k_deblock_down<BPP>, dim3((g.ws + 63) / 64, (g.hs + 3) / 4), dim3(64, 4), 0, ctx->stream, (const uint8_t*)frame, step, g.rh, g.rw,
+                       d->d_small, g.hs, g.ws, g.fast ? g.iscale : 0, inv_area_s, (const int2*)d->d_xr, (const AreaTabEntry*)d->d_xt,
                        (const int2*)d->d_yr, (const AreaTabEntry*)d->d_yt);
     LVK_HIP_CHECK(ctx, hipGetLastError());
-    if ((rc = launch_median<BPP>(ctx, d, hs, ws, (int)s.filter_size)) != LVK_HIP_OK) return rc;
+    if ((rc = launch_median<BPP>(ctx, d, g.hs, g.ws, (int)s.filter_size)) != LVK_HIP_OK) return rc;
 
-    d->rh = rh; d->rw = rw; d->ey = ey; d->ex = ex; d->hs = hs; d->ws = ws; d->have_maps = true;
+    d->rh = g.rh; d->rw = g.rw; d->ey = g.ey; d->ex = g.ex; d->hs = g.hs; d->ws = g.ws; d->have_maps = true;
     if ((rc = launch_blend<BPP>(ctx, frame, step, d)) != LVK_HIP_OK) return rc;
-    if (region_xywh) { region_xywh[0] = 0; region_xywh[1] = 0; region_xywh[2] = rw; region_xywh[3] = rh; }
+    if (region_xywh) { region_xywh[0] = 0; region_xywh[1] = 0; region_xywh[2] = g.rw; region_xywh[3] = g.rh; }
     return LVK_HIP_OK;
 }
 
 } // namespace
+
+// deblock_core.hpp: the two launches the 4:2:0 entry (deblock_420.hip) reuses unchanged
+int deblock::launch_stats_plane(lvk_hip_deblock* d, const uint8_t* plane, int step, const Geometry& g)
+{
+    return launch_stats<1>(d, plane, step, LVK_FORMAT_GRAY, g);
+}
+
+int deblock::launch_median_c3(lvk_hip_deblock* d, const Geometry& g)
+{
+    return launch_median<3>(d->ctx, d, g.hs, g.ws, (int)d->settings.filter_size);
+}
 
 extern "C" {
 

@@ -1,7 +1,8 @@
 """Host-side mirror of lvk::DeblockingFilter (reference: LiveVisionKit/Filters/DeblockingFilter.hpp:26-57) over the C-ABI.
 Same method names: configure / apply / draw_influence / filter_region.  Frames are torch uint8 tensors [rows, cols, 3] on the GPU
 (any row pitch: a view with stride(1) == 3 and stride(2) == 1), filtered IN PLACE like the reference's apply(frame, frame).  apply also takes
-GRAY frames [rows, cols] and BGRA / RGBA frames [rows, cols, 4] (lvk_hip_deblock_apply_gray / _c4)."""
+GRAY frames [rows, cols] and BGRA / RGBA frames [rows, cols, 4] (lvk_hip_deblock_apply_gray / _c4).  apply_yuv420 takes the planes of an I420 / NV12
+frame and writes new planes (lvk_hip_deblock_apply_yuv420)."""
 import ctypes
 
 import numpy as np
@@ -59,6 +60,36 @@ class DeblockingFilter:
             rc = self.lib.lvk_hip_deblock_apply(self.handle, *_frame_args(frame), int(fmt), region)
         self.ctx._check(rc)
         return tuple(region)
+
+    def apply_yuv420(self, y, u, v=None, out=None):
+        """Deblocks the planes of an I420 (y [rows, cols], u, v [rows/2, cols/2]) or NV12 (v=None, u [rows/2, cols/2, 2]) frame OUT OF PLACE in one
+        call (lvk_hip_deblock_apply_yuv420): byte for byte the ingest -> apply(FORMAT_YUV) -> egress chain.  `out` = the output planes in the same
+        layout (allocated when None; rows may be padded: stride(-1) == 1, NV12 UV stride(1) == 2).  Returns (planes, region); asynchronous on the
+        context's stream."""
+        import torch
+        nv12 = v is None
+        planes = (y, u) if nv12 else (y, u, v)
+        if out is None:
+            out = tuple(torch.empty_like(p, memory_format=torch.contiguous_format) for p in planes)
+        out = tuple(out)
+        rows, cols = int(y.shape[0]), int(y.shape[1])
+        if len(out) != len(planes):
+            raise ValueError("`out` holds one plane per input plane")
+        chroma = (rows // 2, cols // 2, 2) if nv12 else (rows // 2, cols // 2)
+        shapes = ((rows, cols), chroma) if nv12 else ((rows, cols), chroma, chroma)
+        for p, shape in zip(planes + out, shapes * 2):
+            if tuple(p.shape) != shape or p.dtype.itemsize != 1 or p.stride(-1) != 1 or (p.dim() == 3 and p.stride(1) != 2):
+                raise ValueError("8-bit planes [rows, cols], [rows/2, cols/2] (NV12: [rows/2, cols/2, 2]) with contiguous rows are required")
+
+        def args(ps):
+            a = []
+            for p in ps:
+                a += [p.data_ptr(), p.stride(0)]
+            return a + ([None, 0] if nv12 else [])
+
+        region = (_c.c_int * 4)()
+        self.ctx._check(self.lib.lvk_hip_deblock_apply_yuv420(self.handle, *args(planes), *args(out), 1 if nv12 else 0, rows, cols, region))
+        return out, tuple(region)
 
     def draw_influence(self, frame, fmt=FORMAT_YUV):
         self.ctx._check(self.lib.lvk_hip_deblock_draw_influence(self.handle, *_frame_args(frame), int(fmt)))
