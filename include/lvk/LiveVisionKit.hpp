@@ -1117,6 +1117,32 @@ public:
         LVK_HIP_ASSERT(settings.output_size.height > 0);
         m_Settings = settings;
     }
+
+    // The plugin's I420 / NV12 planes in one call (lvk_hip_scale_yuv420), byte for byte I4XXIngest / NV12Ingest::to_ocl -> apply(frame, frame) ->
+    // to_obs (Modules/OBS-Plugin/Interop/FrameIngest.cpp:494-602) without the packed frames between them.  Out of place: `output` is created at
+    // output_size with the input's layout and context.  A YUV filter only (yuv_input), for an even output_size that is no smaller than the input.
+    using VideoFilter::apply;
+    void apply(const VideoFrame420& input, VideoFrame420& output, const bool profile = false)
+    {
+        LVK_HIP_ASSERT(!input.empty());
+        LVK_HIP_ASSERT(&input != &output);
+        LVK_HIP_ASSERT(m_Settings.yuv_input);
+        const cv::Size size = m_Settings.output_size;
+        LVK_HIP_ASSERT(size.width % 2 == 0 && size.height % 2 == 0);
+        LVK_HIP_ASSERT(size.width >= input.cols && size.height >= input.rows);
+        m_Ctx = input.context();
+        sync_gpu(profile); frame_timer().start();
+        output.create(size, input.nv12, input.context());
+        LVK_HIP_ASSERT(output.y() != input.y());
+        output.timestamp = input.timestamp;
+        run(input.context(), [&] {
+            m_Ctx->check(lvk_hip_scale_yuv420(m_Ctx->get(), input.y(), input.y_step(), input.u(), input.uv_step(), input.v(), input.uv_step(), input.rows, input.cols,
+                                              output.y(), output.y_step(), output.u(), output.uv_step(), output.v(), output.uv_step(), output.rows, output.cols,
+                                              input.nv12 ? 1 : 0, m_Settings.sharpness),
+                         "ScalingFilter::apply(4:2:0)");
+        });
+        sync_gpu(profile); frame_timer().stop();
+    }
 private:
     void filter(VideoFrame&& input, VideoFrame& output) override
     {

@@ -875,6 +875,7 @@ int lvk_hip_area_resize_path(lvk_hip_ctx* ctx, const void* d_src, int src_step, 
 }
 #endif
 
+#include "lvk_hip_scaling_420.h"  /* lvk_hip_scale_yuv420 (PART 2) */
 #include "lvk_hip_deblock_420.h"  /* lvk_hip_deblock_apply_yuv420 (PART 2) */
 #include "lvk_hip_deblock_px.h"   /* lvk_hip_deblock_apply_gray / _c4 (PART 2) */
 #endif /* LVK_HIP_H */

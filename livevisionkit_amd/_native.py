@@ -185,6 +185,12 @@ _SIG_DEBLOCK_420 = {
                                                 _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
 }
 
+# what include/lvk_hip_scaling_420.h declares (lvk_hip.h includes it; its pin: tests/test_scaling_420_spec.py)
+_SIG_SCALING_420 = {
+    "lvk_hip_scale_yuv420": (_c.c_int, [_P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int,
+                                        _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float]),
+}
+
 _lib = None
 
 
@@ -203,6 +209,11 @@ def symbols_deblock_420():
     return sorted(_SIG_DEBLOCK_420.keys())
 
 
+def symbols_scaling_420():
+    """The names include/lvk_hip_scaling_420.h declares."""
+    return sorted(_SIG_SCALING_420.keys())
+
+
 def load():
     """Load liblvk_hip.so and bind every declared symbol; raises if the library or a symbol is missing."""
     global _lib
@@ -214,7 +225,7 @@ def load():
             "(or `make -C livevisionkit_amd/csrc`). There is no CPU fallback.")
     import torch  # noqa: F401  (loads the process-wide HIP runtime first)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX, **_SIG_DEBLOCK_420}.items():
+    for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX, **_SIG_DEBLOCK_420, **_SIG_SCALING_420}.items():
         fn = getattr(lib, name)      # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

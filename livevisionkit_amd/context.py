@@ -417,6 +417,25 @@ class Context:
                                              float(sharpness)))
         return out
 
+    def scale_yuv420(self, y, u, v=None, size=None, sharpness=0.8, out=None):
+        """lvk_hip_scale_yuv420: lvk::ScalingFilter on I420 (y, u, v) or NV12 (y, uv[r/2, c/2, 2]; v=None) planes in one call, out of place: the planes of
+        ingest_yuv420 -> upscale(size, yuv=True) -> sharpen(sharpness) -> egress_yuv420.  size = (width, height), even and >= the input's; None: the
+        input's (sharpen only).  out: the output planes, (y, u, v) or (y, uv).  Returns them."""
+        import torch
+        rows, cols = y.shape
+        w, h = (cols, rows) if size is None else (int(size[0]), int(size[1]))
+        nv12 = v is None
+        if out is None:
+            oy = torch.empty((h, w), dtype=torch.uint8, device=y.device)
+            ou = torch.empty((h // 2, w // 2, 2) if nv12 else (h // 2, w // 2), dtype=torch.uint8, device=y.device)
+            out = (oy, ou) if nv12 else (oy, ou, torch.empty_like(ou))
+        out = tuple(out)
+        vv, ov = (u, out[1]) if nv12 else (v, out[2])
+        self._check(self.lib.lvk_hip_scale_yuv420(self.handle, y.data_ptr(), y.stride(0), u.data_ptr(), u.stride(0), vv.data_ptr(), vv.stride(0), rows, cols,
+                                                  out[0].data_ptr(), out[0].stride(0), out[1].data_ptr(), out[1].stride(0), ov.data_ptr(), ov.stride(0),
+                                                  h, w, 1 if nv12 else 0, float(sharpness)))
+        return out
+
     # ---- ScalingFilter's two steps on one-channel ([rows, cols]) and four-channel ([rows, cols, 4]; 4-byte aligned, pitches multiples of 4) frames ----
     def _px_upscale(self, sfx, src, size, out):
         out = self._px_out(sfx, src, out, (int(size[1]), int(size[0])))

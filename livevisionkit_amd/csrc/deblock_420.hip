@@ -7,22 +7,16 @@
 //   k_deblock_blend_420     one thread per 4 x 2 luma pixels and their 2 chroma samples per plane: up-samples the chroma, blends the pixels inside
 //                           the region as k_deblock_blend does, writes the luma and the (sum + 2) >> 2 of each 2 x 2 quad of chroma values
 //
-// up() is the exact 2x chroma up-sampling of the ingest; its closed form is derived in the comment above k_ingest_yuv420_x2 (ingest.hip) and restated
-// here.  For luma column x with c = x / 2 the horizontal sum is t = 3 C[c] + C[f], f = c - 1 for an even x and c + 1 for an odd one; for luma row y
-// with k = y / 2 the value is (((3 t_k) >> 2) + (t_g >> 2) + 2) >> 2, g = k - 1 for an even y and k + 1 for an odd one; f and g are clamped to the
-// plane (the edge sample replicated, coefficients unchanged).
+// up() is the exact 2x chroma up-sampling of the ingest in the closed form yuv420_core.hpp restates.
 // No load touches a byte outside the cols (Y, NV12 UV) or cols / 2 (I420 chroma) bytes of a plane row, and no store one outside those of an
 // output row.
 #include "deblock_core.hpp"
+#include "yuv420_core.hpp"
 
 using namespace deblock;
+using namespace yuv420;
 
 namespace {
-
-struct Planes { const uint8_t* y; const uint8_t* u; const uint8_t* v; int ys, us, vs; };     // NV12: u is the UV plane, v unused
-struct PlanesOut { uint8_t* y; uint8_t* u; uint8_t* v; int ys, us, vs; };
-
-__device__ __forceinline__ int up_v(int t_near, int t_far) { return (((3 * t_near) >> 2) + (t_far >> 2) + 2) >> 2; }
 
 // Row y of the frame as the ingest makes it: the luma row and, per chroma plane, the row the up-sampling weighs 3 (n: k = y / 2) and the one it
 // weighs 1 (f: k - 1 for an even y, k + 1 for an odd one, clamped to the plane)
@@ -50,39 +44,6 @@ __device__ __forceinline__ uint32_t pixel_420(const Row420& r, int cc, int x)
     const int u = up_v(3 * r.un[c * PIX] + r.un[cf * PIX], 3 * r.uf[c * PIX] + r.uf[cf * PIX]);
     const int v = up_v(3 * r.vn[c * PIX] + r.vn[cf * PIX], 3 * r.vf[c * PIX] + r.vf[cf * PIX]);
     return (uint32_t)r.y[x] | ((uint32_t)u << 8) | ((uint32_t)v << 16);
-}
-
-struct __attribute__((packed, aligned(1))) P4 { uint32_t w; };
-struct __attribute__((packed, aligned(1))) P8 { uint32_t w[2]; };
-
-// chroma columns c0 - 1 .. c0 + 2 of one chroma row, one sample per byte (su: U, sv: V), columns clamped to the plane.  Inside the plane: one
-// unaligned dword per plane (NV12: one 8-byte load, de-interleaved with v_perm_b32), as the ingest reads them.
-template <bool NV12>
-__device__ __forceinline__ void load_chroma4(const uint8_t* __restrict__ urow, const uint8_t* __restrict__ vrow, int c0, int cc, uint32_t& su, uint32_t& sv)
-{
-    if (c0 >= 1 && c0 + 2 < cc)
-    {
-        if constexpr (NV12)
-        {
-            const P8 a = *reinterpret_cast<const P8*>(urow + 2 * (c0 - 1));
-            su = __builtin_amdgcn_perm(a.w[1], a.w[0], 0x06040200u); sv = __builtin_amdgcn_perm(a.w[1], a.w[0], 0x07050301u);
-        }
-        else
-        {
-            su = reinterpret_cast<const P4*>(urow + c0 - 1)->w;
-            sv = reinterpret_cast<const P4*>(vrow + c0 - 1)->w;
-        }
-        return;
-    }
-    constexpr int PIX = NV12 ? 2 : 1;
-    su = sv = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-    {
-        const int c = min(max(c0 - 1 + j, 0), cc - 1);
-        su |= (uint32_t)urow[c * PIX] << (8 * j);
-        sv |= (uint32_t)(NV12 ? urow[c * PIX + 1] : vrow[c * PIX]) << (8 * j);
-    }
 }
 
 // A pixel of the median frame (three bytes, any alignment) as ONE load: the dword at its address, whose fourth byte is the next pixel's first or,
@@ -291,19 +252,6 @@ void k_deblock_blend_420(Planes in, PlanesOut out, int rows, int cols, int rh, i
         }
     }
 }
-
-// [first byte, one past the last byte) of a plane of `prows` rows of `row` bytes at pitch `step`
-struct Span { uintptr_t lo, hi; };
-
-Span span_of(const void* p, int step, int prows, int row)
-{
-    const uintptr_t lo = (uintptr_t)p;
-    return {lo, lo + (uintptr_t)(prows - 1) * (uintptr_t)step + (uintptr_t)row};
-}
-
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-bool aligned_to(const void* p, int step, unsigned a) { return (((uintptr_t)p | (uintptr_t)step) & (a - 1)) == 0; }
 
 } // namespace
 
