@@ -1223,6 +1223,9 @@ using GridDetectorSettings = FeatureDetectorSettings;
 // the OBS plugin's CAS filter (Sources/Enhancement/CASFilter.cpp, Effects/CASEffect.cpp)
 #include "CASFilter.hpp"
 
+// the OBS plugin's lens-correction filter (Sources/Enhancement/LCFilter.cpp)
+#include "LCFilter.hpp"
+
 // Filters/ConversionFilter.hpp
 #include "ConversionFilter.hpp"
 

@@ -871,6 +871,46 @@ enum
 int lvk_hip_area_resize_path(lvk_hip_ctx* ctx, const void* d_src, int src_step, int pix_stride, int channel,
                              int srows, int scols, int drows, int dcols);
 
+/* ---- lvk::LCFilter: the OBS plugin's lens correction (Modules/OBS-Plugin/Sources/Enhancement/LCFilter.cpp:133-192) as an object ---------------------
+ * DESIGN.md section 27.  First the one primitive it adds, the counterpart of lvk_hip_warpmesh_apply_yuv420 for a materialised map: d_src is a packed YUV
+ * 8UC3 frame, d_map a rows x cols float2 offset map in pixels (what lvk_hip_lens_map_create builds; 8-byte aligned, map_step a multiple of 8), the output
+ * I420 (o_y, o_u, o_v) or NV12 (o_y, o_u = the UV plane, o_v ignored) planes: byte for byte lvk_hip_remap_map(.., yuv = 1) followed by
+ * lvk_hip_egress_yuv420, in one kernel, in the context's remap precision.  Asynchronous on the context's stream.  Refused with LVK_HIP_ERR_ARG, nothing
+ * written: a NULL pointer that is in use, odd rows or cols or either below 2, a pitch below its row, a map lvk_hip_remap_map refuses, the source's or the
+ * map's byte range overlapping an output plane, two output planes overlapping. */
+int lvk_hip_remap_map_yuv420(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols,
+                             void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int nv12,
+                             const void* d_map, int map_step, const uint8_t bg[3]);
+/* The filter.  It owns the camera profile (NULL: none selected -- frames pass through), the offset map of the LAST frame size -- built at the first apply,
+ * again when the frame size or the profile changed (`m_MeshOutdated || size != frame.size()`), the old map released behind the stream -- and the test
+ * mode: lvk::draw_grid(frame, {32, 32}, col::MAGENTA[format], 1), (105, 212, 234) on YUV and (255, 0, 255) on BGR / RGB frames, drawn BEFORE the warp and
+ * warped with the frame.  Background (0, 0, 0[, 0]), WarpMesh::apply's default; the YUV EASU program for LVK_FORMAT_YUV, the RGB one otherwise.  Applies
+ * are asynchronous on the context's stream and out of place (overlapping source and destination are refused); the map build is synchronous host work.
+ *   _configure         a profile with fx == 0 or fy == 0 is refused and leaves the object as it was (so does _create: no object).
+ *   _view              the valid-pixel region of cv::getOptimalNewCameraMatrix (x, y, w, h) for a rows x cols frame; the whole frame without a profile.
+ *   _apply             three channels (LVK_FORMAT_BGR, _RGB, _YUV): [lvk_hip_draw_grid into d_src] -> lvk_hip_remap_map(d_src -> d_dst); a copy without a
+ *                      profile.  IN TEST MODE THE GRID IS DRAWN INTO THE CALLER'S SOURCE FRAME, as the reference draws into the frame it is handed;
+ *                      outside test mode d_src is not written.
+ *   _apply_gray / _c4  lvk_hip_remap_map_gray / _c4 (LVK_FORMAT_BGRA, _RGBA) with the same map; a copy without a profile.  DECLARED GAP: the grid kernel
+ *                      writes three bytes per pixel, so both are refused in test mode (LVK_HIP_ERR_ARG, nothing written), like the stabilizer's overlays.
+ *   _apply_yuv420      I420 / NV12 planes in, planes out (NV12: d_u / o_u are the UV planes, d_v / o_v ignored): byte for byte lvk_hip_ingest_yuv420 ->
+ *                      [lvk_hip_draw_grid, YUV magenta] -> lvk_hip_remap_map(yuv = 1, bg 0, 0, 0) -> lvk_hip_egress_yuv420, the remap and the egress as one
+ *                      kernel; without a profile ingest -> [grid] -> egress (the chroma is the up- and down-sampled chroma, as in the plugin).  The packed
+ *                      frame in between is a block of the context's pool that returns to it inside the call; the input planes are never written.
+ *                      Refused with LVK_HIP_ERR_ARG, nothing written or enqueued: a NULL plane that is in use, odd rows or cols or either below 2, a pitch
+ *                      below its row, an input plane overlapping an output plane, two output planes overlapping.
+ * A NULL object is refused.  The object must be destroyed before its context. */
+typedef struct lvk_hip_lens lvk_hip_lens;
+int  lvk_hip_lens_create(lvk_hip_ctx* ctx, const lvk_camera_params* profile /* NULL: none selected */, int test_mode, lvk_hip_lens** out);
+int  lvk_hip_lens_configure(lvk_hip_lens* lens, const lvk_camera_params* profile, int test_mode);
+void lvk_hip_lens_destroy(lvk_hip_lens* lens);
+int  lvk_hip_lens_view(lvk_hip_lens* lens, int rows, int cols, int view_xywh[4]);
+int  lvk_hip_lens_apply(lvk_hip_lens* lens, void* d_src, int src_step, int rows, int cols, int format, void* d_dst, int dst_step);
+int  lvk_hip_lens_apply_gray(lvk_hip_lens* lens, const void* d_src, int src_step, int rows, int cols, void* d_dst, int dst_step);
+int  lvk_hip_lens_apply_c4(lvk_hip_lens* lens, const void* d_src, int src_step, int rows, int cols, int format, void* d_dst, int dst_step);
+int  lvk_hip_lens_apply_yuv420(lvk_hip_lens* lens, const void* d_y, int y_step, const void* d_u, int u_step, const void* d_v, int v_step,
+                               void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int rows, int cols, int nv12);
+
 #ifdef __cplusplus
 }
 #endif

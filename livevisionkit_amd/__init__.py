@@ -12,8 +12,9 @@ from .cas import CASFilter
 from .convert import ConversionFilter, reformat
 from .fsr import FSRFilter, fsr_geometry, easu_const
 from .draw import draw_points, draw_rect, draw_text, text_size
+from .lens import LCFilter
 from . import shard
 
 __all__ = ["Context", "LvkHipError", "REMAP_EXACT", "REMAP_1LSB", "StabilizationFilter", "StabilizationFilterSettings", "DeblockingFilter", "DeblockingFilterSettings", "CASFilter",
-           "ConversionFilter", "reformat", "FSRFilter", "fsr_geometry", "easu_const", "draw_points", "draw_rect",
+           "ConversionFilter", "reformat", "FSRFilter", "fsr_geometry", "easu_const", "LCFilter", "draw_points", "draw_rect",
            "draw_text", "text_size", "_native"]

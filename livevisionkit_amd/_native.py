@@ -171,6 +171,17 @@ _SIG = {
     "lvk_hip_fsr_easu_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _P, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_fsr_easu_gray_path": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "lvk_hip_area_resize_path": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_remap_map_yuv420": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int,
+                                            _P, _c.c_int, _c.POINTER(_c.c_uint8)]),
+    "lvk_hip_lens_create": (_c.c_int, [_P, _P, _c.c_int, _c.POINTER(_P)]),
+    "lvk_hip_lens_configure": (_c.c_int, [_P, _P, _c.c_int]),
+    "lvk_hip_lens_destroy": (None, [_P]),
+    "lvk_hip_lens_view": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+    "lvk_hip_lens_apply": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int]),
+    "lvk_hip_lens_apply_gray": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int]),
+    "lvk_hip_lens_apply_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int]),
+    "lvk_hip_lens_apply_yuv420": (_c.c_int, [_P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int,
+                                             _c.c_int, _c.c_int, _c.c_int]),
 }
 
 # what include/lvk_hip_deblock_px.h declares (lvk_hip.h includes it; the header has its own pin, tests/test_deblock_px_spec.py)

@@ -397,6 +397,23 @@ class Context:
                                                offsets.data_ptr(), offsets.stride(0) * 4, bgp, 1 if yuv else 0))
         return out
 
+    def remap_map_yuv420(self, src, offsets, bg=(255, 0, 255), nv12=False, out=None):
+        """lvk_hip_remap_map_yuv420: remap_map(yuv=True) + 4:2:0 egress in one kernel: packed YUV [rows, cols, 3] and offsets [rows, cols, 2] -> (y, u, v)
+        I420 or (y, uv) NV12 planes (`out`: the planes to write; allocated when None)."""
+        import torch
+        rows, cols = src.shape[0], src.shape[1]
+        if out is None:
+            y = torch.empty((rows, cols), dtype=torch.uint8, device=src.device)
+            u = torch.empty((rows // 2, cols // 2, 2) if nv12 else (rows // 2, cols // 2), dtype=torch.uint8, device=src.device)
+            out = (y, u) if nv12 else (y, u, torch.empty_like(u))
+        out = tuple(out)
+        v = out[1] if nv12 else out[2]
+        bga, bgp = _u8x3(bg)
+        self._check(self.lib.lvk_hip_remap_map_yuv420(self.handle, src.data_ptr(), src.stride(0), rows, cols, out[0].data_ptr(), out[0].stride(0),
+                                                      out[1].data_ptr(), out[1].stride(0), v.data_ptr(), v.stride(0), 1 if nv12 else 0,
+                                                      offsets.data_ptr(), offsets.stride(0) * 4, bgp))
+        return out
+
     def upscale(self, src, size, yuv=True, out=None):
         """lvk::upscale(src, dst, size, yuv): EASU upsampling to size = (width, height) >= the source size."""
         import torch

@@ -71,7 +71,10 @@ void optimal_matrix(const lvk_camera_params& c, int rows, int cols, double P[4],
     if (view[2] <= 0 || view[3] <= 0) view[0] = view[1] = view[2] = view[3] = 0;
 }
 
-void build_offsets(const lvk_camera_params& c, int rows, int cols, std::vector<float>& off, int view[4])
+} // namespace
+
+// LCFilter::prepare_undistort_maps: the rows x cols x 2 offset map (pixels) and the view region of profile c (lvk_hip_lens_map_create, the lens filter object)
+void lvk_lens_build_offsets(const lvk_camera_params& c, int rows, int cols, std::vector<float>& off, int view[4])
 {
     double P[4];
     optimal_matrix(c, rows, cols, P, view);
@@ -99,6 +102,8 @@ void build_offsets(const lvk_camera_params& c, int rows, int cols, std::vector<f
         }
     }
 }
+
+namespace {
 
 // One thread per point (lvk_lens_undistort_point, lvk_hip_internal.hpp)
 __global__ void k_lens_undistort(LensModelD M, double sx, double sy, const float2* __restrict__ a, int na,
@@ -170,7 +175,7 @@ int lvk_hip_lens_map_create(lvk_hip_ctx* ctx, const lvk_camera_params* params, i
     LVK_HIP_ENTRY(ctx);
     LVK_HIP_REQUIRE(ctx, params && d_map && rows > 1 && cols > 1 && params->fx != 0.0 && params->fy != 0.0);
     std::vector<float> off; int view[4];
-    build_offsets(*params, rows, cols, off, view);
+    lvk_lens_build_offsets(*params, rows, cols, off, view);
     void* d = nullptr;
     LVK_HIP_CHECK(ctx, hipMalloc(&d, off.size() * sizeof(float)));
     hipError_t e = hipMemcpy(d, off.data(), off.size() * sizeof(float), hipMemcpyHostToDevice);

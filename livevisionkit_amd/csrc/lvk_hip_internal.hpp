@@ -382,6 +382,8 @@ __device__ __forceinline__ float2 lvk_lens_undistort_point(const LensModelD& M, 
 }
 struct LensArgs { float f[17]; };
 int lvk_lens_model_build(const lvk_camera_params& params, int rows, int cols, LensModel& out);
+// the materialised map of the same profile: rows x cols x 2 offsets in pixels, tightly packed, and the view region (x, y, w, h); rows, cols > 1, fx, fy != 0
+void lvk_lens_build_offsets(const lvk_camera_params& params, int rows, int cols, std::vector<float>& offsets, int view[4]);
 // (a | b)[i] raw tracking-frame points -> lens-corrected positions, binary64, written to out[0 .. na + nb)
 int lvk_launch_lens_undistort(lvk_hip_ctx* ctx, hipStream_t stream, const LensModel& model, double sx, double sy,
                               const float2* a, int na, const float2* b, int nb, float2* out);
