@@ -25,6 +25,22 @@ def _u8x4(bg):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
 
+def _planes420_empty(rows, cols, nv12, device):
+    """New output planes of a rows x cols 4:2:0 frame: (y, u, v) for I420, (y, uv [rows/2, cols/2, 2]) for NV12."""
+    import torch
+    y = torch.empty((rows, cols), dtype=torch.uint8, device=device)
+    u = torch.empty((rows // 2, cols // 2, 2) if nv12 else (rows // 2, cols // 2), dtype=torch.uint8, device=device)
+    return (y, u) if nv12 else (y, u, torch.empty_like(u))
+
+
+def _planes420_args(planes, nv12):
+    """A plane tuple as the C entries take it: [y, y_step, u, u_step, v, v_step]; NV12 has no V plane (NULL, 0)."""
+    a = []
+    for p in planes[:2 if nv12 else 3]:
+        a += [p.data_ptr(), p.stride(0)]
+    return a + ([None, 0] if nv12 else [])
+
+
 TRACK_CHAIN_GUARD = 64        # LVK_TRACK_CHAIN_GUARD: entries in front of and behind the flow kernel's output buffers
 TRACK_CHAIN_FILL = 0xA5       # LVK_TRACK_CHAIN_FILL: every output byte no kernel wrote
 
@@ -335,24 +351,15 @@ class Context:
         if out is None:
             out = torch.empty((rows, cols, 3), dtype=torch.uint8, device=y.device)
         nv12 = v is None
-        vv = u if nv12 else v
-        self._check(self.lib.lvk_hip_ingest_yuv420(self.handle, y.data_ptr(), y.stride(0), u.data_ptr(), u.stride(0), vv.data_ptr(), vv.stride(0),
-                                                   1 if nv12 else 0, rows, cols, out.data_ptr(), out.stride(0)))
+        self._check(self.lib.lvk_hip_ingest_yuv420(self.handle, *_planes420_args((y, u, v), nv12), 1 if nv12 else 0, rows, cols, out.data_ptr(), out.stride(0)))
         return out
 
     def egress_yuv420(self, frame, nv12=False, out=None):
-        import torch
         rows, cols = frame.shape[:2]
         if out is None:
-            y = torch.empty((rows, cols), dtype=torch.uint8, device=frame.device)
-            if nv12:
-                u = torch.empty((rows // 2, cols // 2, 2), dtype=torch.uint8, device=frame.device); v = u
-            else:
-                u = torch.empty((rows // 2, cols // 2), dtype=torch.uint8, device=frame.device); v = torch.empty_like(u)
-        else:
-            y, u, v = out if not nv12 else (out[0], out[1], out[1])
-        self._check(self.lib.lvk_hip_egress_yuv420(self.handle, frame.data_ptr(), frame.stride(0), rows, cols, y.data_ptr(), y.stride(0),
-                                                   u.data_ptr(), u.stride(0), v.data_ptr(), v.stride(0), 1 if nv12 else 0))
+            out = _planes420_empty(rows, cols, nv12, frame.device)
+        y, u, v = out if not nv12 else (out[0], out[1], None)
+        self._check(self.lib.lvk_hip_egress_yuv420(self.handle, frame.data_ptr(), frame.stride(0), rows, cols, *_planes420_args((y, u, v), nv12), 1 if nv12 else 0))
         return (y, u) if nv12 else (y, u, v)
 
     # ---- every OBS video format of FrameIngest::Select (Modules/OBS-Plugin/Interop/FrameIngest.cpp:36-75) ----------------------
@@ -400,17 +407,10 @@ class Context:
     def remap_map_yuv420(self, src, offsets, bg=(255, 0, 255), nv12=False, out=None):
         """lvk_hip_remap_map_yuv420: remap_map(yuv=True) + 4:2:0 egress in one kernel: packed YUV [rows, cols, 3] and offsets [rows, cols, 2] -> (y, u, v)
         I420 or (y, uv) NV12 planes (`out`: the planes to write; allocated when None)."""
-        import torch
         rows, cols = src.shape[0], src.shape[1]
-        if out is None:
-            y = torch.empty((rows, cols), dtype=torch.uint8, device=src.device)
-            u = torch.empty((rows // 2, cols // 2, 2) if nv12 else (rows // 2, cols // 2), dtype=torch.uint8, device=src.device)
-            out = (y, u) if nv12 else (y, u, torch.empty_like(u))
-        out = tuple(out)
-        v = out[1] if nv12 else out[2]
+        out = _planes420_empty(rows, cols, nv12, src.device) if out is None else tuple(out)
         bga, bgp = _u8x3(bg)
-        self._check(self.lib.lvk_hip_remap_map_yuv420(self.handle, src.data_ptr(), src.stride(0), rows, cols, out[0].data_ptr(), out[0].stride(0),
-                                                      out[1].data_ptr(), out[1].stride(0), v.data_ptr(), v.stride(0), 1 if nv12 else 0,
+        self._check(self.lib.lvk_hip_remap_map_yuv420(self.handle, src.data_ptr(), src.stride(0), rows, cols, *_planes420_args(out, nv12), 1 if nv12 else 0,
                                                       offsets.data_ptr(), offsets.stride(0) * 4, bgp))
         return out
 
@@ -438,18 +438,11 @@ class Context:
         """lvk_hip_scale_yuv420: lvk::ScalingFilter on I420 (y, u, v) or NV12 (y, uv[r/2, c/2, 2]; v=None) planes in one call, out of place: the planes of
         ingest_yuv420 -> upscale(size, yuv=True) -> sharpen(sharpness) -> egress_yuv420.  size = (width, height), even and >= the input's; None: the
         input's (sharpen only).  out: the output planes, (y, u, v) or (y, uv).  Returns them."""
-        import torch
         rows, cols = y.shape
         w, h = (cols, rows) if size is None else (int(size[0]), int(size[1]))
         nv12 = v is None
-        if out is None:
-            oy = torch.empty((h, w), dtype=torch.uint8, device=y.device)
-            ou = torch.empty((h // 2, w // 2, 2) if nv12 else (h // 2, w // 2), dtype=torch.uint8, device=y.device)
-            out = (oy, ou) if nv12 else (oy, ou, torch.empty_like(ou))
-        out = tuple(out)
-        vv, ov = (u, out[1]) if nv12 else (v, out[2])
-        self._check(self.lib.lvk_hip_scale_yuv420(self.handle, y.data_ptr(), y.stride(0), u.data_ptr(), u.stride(0), vv.data_ptr(), vv.stride(0), rows, cols,
-                                                  out[0].data_ptr(), out[0].stride(0), out[1].data_ptr(), out[1].stride(0), ov.data_ptr(), ov.stride(0),
+        out = _planes420_empty(h, w, nv12, y.device) if out is None else tuple(out)
+        self._check(self.lib.lvk_hip_scale_yuv420(self.handle, *_planes420_args((y, u, v), nv12), rows, cols, *_planes420_args(out, nv12),
                                                   h, w, 1 if nv12 else 0, float(sharpness)))
         return out
 
@@ -614,20 +607,14 @@ class Context:
 
     def warpmesh_apply_yuv420(self, src, mesh, bg=(255, 0, 255), nv12=False):
         """WarpMesh::apply + 4:2:0 egress in one kernel: packed YUV [rows, cols, 3] -> (y, u, v) I420 or (y, uv) NV12 planes."""
-        import torch
         rows, cols = src.shape[0], src.shape[1]
-        y = torch.empty((rows, cols), dtype=torch.uint8, device=src.device)
-        if nv12:
-            u = torch.empty((rows // 2, cols // 2, 2), dtype=torch.uint8, device=src.device); v = u
-        else:
-            u = torch.empty((rows // 2, cols // 2), dtype=torch.uint8, device=src.device); v = torch.empty_like(u)
+        out = _planes420_empty(rows, cols, nv12, src.device)
         m = np.ascontiguousarray(mesh, dtype=np.float32)
         ma, mp = _f32(m)
         bga, bgp = _u8x3(bg)
-        self._check(self.lib.lvk_hip_warpmesh_apply_yuv420(self.handle, src.data_ptr(), src.stride(0), rows, cols, y.data_ptr(), y.stride(0),
-                                                           u.data_ptr(), u.stride(0), v.data_ptr(), v.stride(0), 1 if nv12 else 0,
+        self._check(self.lib.lvk_hip_warpmesh_apply_yuv420(self.handle, src.data_ptr(), src.stride(0), rows, cols, *_planes420_args(out, nv12), 1 if nv12 else 0,
                                                            mp, m.shape[0], m.shape[1], bgp))
-        return (y, u) if nv12 else (y, u, v)
+        return out
 
 
 class MeshSolver:

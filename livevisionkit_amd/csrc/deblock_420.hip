@@ -103,9 +103,6 @@ void k_deblock_down_420(Planes in, int rows, int cols, int rh, int rw, uint8_t* 
                   d, x, y, rh, rw, iscale, inv_area, xr, xt, yr, yt);
 }
 
-// flags of k_deblock_blend_420: which of the wide accesses the planes' bases and pitches allow
-constexpr int kYInDw = 1, kYOutDw = 2, kChromaWide = 4;
-
 // One thread per group of 4 x 2 luma pixels (columns 4 g .. 4 g + 3, rows 2 k and 2 k + 1; the last group of a row holds 2 columns where
 // cols % 4 == 2) and the chroma samples (c0, k), (c0 + 1, k), c0 = 2 g.  The chroma rows k - 1 .. k + 1 and columns c0 - 1 .. c0 + 2 are read once;
 // the horizontal sums of row k serve both luma rows.  A pixel inside the region (x < rw, y < rh) is blended channel by channel as k_deblock_blend
@@ -120,7 +117,7 @@ void k_deblock_blend_420(Planes in, PlanesOut out, int rows, int cols, int rh, i
     const int g = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y * 4 + threadIdx.y;
     const int x0 = g * 4, cc = cols >> 1, cr = rows >> 1;
     if (x0 >= cols || k >= cr) return;
-    const bool four = x0 + 4 <= cols;                       // else the row's last two columns
+    const bool half = x0 + 4 > cols;                        // the row's last two columns
     const int c0 = x0 >> 1, ya = 2 * k;
 
     // chroma: rows k - 1, k, k + 1 (clamped), horizontal sums per row
@@ -139,11 +136,11 @@ void k_deblock_blend_420(Planes in, PlanesOut out, int rows, int cols, int rh, i
     for (int r = 0; r < 2; r++)
     {
         const uint8_t* p = in.y + (size_t)(ya + r) * in.ys + x0;
-        if (four && (flags & kYInDw)) yw[r] = *reinterpret_cast<const uint32_t*>(p);
+        if (!half && (flags & kYInDw)) yw[r] = *reinterpret_cast<const uint32_t*>(p);
         else
         {
             yw[r] = (uint32_t)p[0] | ((uint32_t)p[1] << 8);
-            if (four) yw[r] |= ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+            if (!half) yw[r] |= ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
         }
     }
     // the group's pixels: Y in yw, up(U) / up(V) in U / V; row 0 = luma row 2 k (chroma rows k - 1, k), row 1 = 2 k + 1 (k, k + 1)
@@ -215,42 +212,13 @@ void k_deblock_blend_420(Planes in, PlanesOut out, int rows, int cols, int rh, i
 #pragma unroll
     for (int r = 0; r < 2; r++)
     {
-        uint8_t* p = out.y + (size_t)(ya + r) * out.ys + x0;
-        if (four && (flags & kYOutDw)) *reinterpret_cast<uint32_t*>(p) = yw[r];
-        else
-        {
-            p[0] = (uint8_t)yw[r]; p[1] = (uint8_t)(yw[r] >> 8);
-            if (four) { p[2] = (uint8_t)(yw[r] >> 16); p[3] = (uint8_t)(yw[r] >> 24); }
-        }
+        const uint32_t y[4] = {yw[r], yw[r] >> 8, yw[r] >> 16, yw[r] >> 24};
+        store_luma4(out.y + (size_t)(ya + r) * out.ys + x0, y, half, flags);
     }
     // chroma out: INTER_AREA 0.5 of each 2 x 2 quad
-    const uint32_t u0 = (uint32_t)(U[0][0] + U[0][1] + U[1][0] + U[1][1] + 2) >> 2, u1 = (uint32_t)(U[0][2] + U[0][3] + U[1][2] + U[1][3] + 2) >> 2;
-    const uint32_t v0 = (uint32_t)(V[0][0] + V[0][1] + V[1][0] + V[1][1] + 2) >> 2, v1 = (uint32_t)(V[0][2] + V[0][3] + V[1][2] + V[1][3] + 2) >> 2;
-    if constexpr (NV12)
-    {
-        uint8_t* p = out.u + (size_t)k * out.us + 2 * c0;
-        if (four && (flags & kChromaWide)) *reinterpret_cast<uint32_t*>(p) = u0 | (v0 << 8) | (u1 << 16) | (v1 << 24);
-        else
-        {
-            p[0] = (uint8_t)u0; p[1] = (uint8_t)v0;
-            if (four) { p[2] = (uint8_t)u1; p[3] = (uint8_t)v1; }
-        }
-    }
-    else
-    {
-        uint8_t* pu = out.u + (size_t)k * out.us + c0;
-        uint8_t* pv = out.v + (size_t)k * out.vs + c0;
-        if (four && (flags & kChromaWide))
-        {
-            *reinterpret_cast<uint16_t*>(pu) = (uint16_t)(u0 | (u1 << 8));
-            *reinterpret_cast<uint16_t*>(pv) = (uint16_t)(v0 | (v1 << 8));
-        }
-        else
-        {
-            pu[0] = (uint8_t)u0; pv[0] = (uint8_t)v0;
-            if (four) { pu[1] = (uint8_t)u1; pv[1] = (uint8_t)v1; }
-        }
-    }
+    const uint32_t u[2] = {(uint32_t)(U[0][0] + U[0][1] + U[1][0] + U[1][1] + 2) >> 2, (uint32_t)(U[0][2] + U[0][3] + U[1][2] + U[1][3] + 2) >> 2};
+    const uint32_t v[2] = {(uint32_t)(V[0][0] + V[0][1] + V[1][0] + V[1][1] + 2) >> 2, (uint32_t)(V[0][2] + V[0][3] + V[1][2] + V[1][3] + 2) >> 2};
+    store_chroma2<NV12>(out, k, c0, u, v, half, flags);
 }
 
 } // namespace
@@ -263,31 +231,20 @@ extern "C" int lvk_hip_deblock_apply_yuv420(lvk_hip_deblock* d, const void* d_y,
     lvk_hip_ctx* ctx = d->ctx;
     LVK_HIP_ENTRY(ctx);
     const std::string name("lvk_hip_deblock_apply_yuv420");
-    LVK_HIP_REQUIRE(ctx, d_y && d_u && (nv12 || d_v) && o_y && o_u && (nv12 || o_v));
-    LVK_HIP_REQUIRE(ctx, rows > 0 && cols > 0 && (rows & 1) == 0 && (cols & 1) == 0);       // 4:2:0 needs even dimensions
-    const int crow = nv12 ? cols : cols / 2, crows = rows / 2;                               // bytes of a chroma row, chroma rows
-    LVK_HIP_REQUIRE(ctx, y_step >= cols && oy_step >= cols && u_step >= crow && ou_step >= crow && (nv12 || (v_step >= crow && ov_step >= crow)));
-    {
-        // out of place: the chroma up-sampling reads its neighbours, so no input byte may be an output byte, and no output byte another's
-        const int n = nv12 ? 2 : 3;
-        const Span in[3] = {span_of(d_y, y_step, rows, cols), span_of(d_u, u_step, crows, crow), span_of(nv12 ? d_u : d_v, nv12 ? u_step : v_step, crows, crow)};
-        const Span out[3] = {span_of(o_y, oy_step, rows, cols), span_of(o_u, ou_step, crows, crow), span_of(nv12 ? o_u : o_v, nv12 ? ou_step : ov_step, crows, crow)};
-        for (int i = 0; i < n; i++)
-        {
-            for (int j = 0; j < n; j++)
-                if (overlap(in[j], out[i])) return ctx->fail(LVK_HIP_ERR_ARG, name + ": an output plane overlaps an input plane (the call is out of place)");
-            for (int j = i + 1; j < n; j++)
-                if (overlap(out[i], out[j])) return ctx->fail(LVK_HIP_ERR_ARG, name + ": two output planes overlap");
-        }
-    }
+    const PlaneSet src = plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols), dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols);
+    LVK_HIP_REQUIRE(ctx, well_formed(src) && well_formed(dst));
+    int rc;
+    // out of place: the chroma up-sampling reads its neighbours
+    const Spans src_spans = spans_of(src);
+    if ((rc = require_out_of_place(ctx, name.c_str(), src_spans.s, src_spans.n, dst)) != LVK_HIP_OK) return rc;
     const lvk_deblock_settings& s = d->settings;
     Geometry g;
-    int rc;
     if ((rc = geometry(ctx, s, rows, cols, name, g)) != LVK_HIP_OK) return rc;
     if ((rc = reserve(d, g, 3)) != LVK_HIP_OK) return rc;
 
-    const Planes in{(const uint8_t*)d_y, (const uint8_t*)d_u, (const uint8_t*)(nv12 ? d_u : d_v), y_step, u_step, nv12 ? u_step : v_step};
-    const PlanesOut out{(uint8_t*)o_y, (uint8_t*)o_u, (uint8_t*)(nv12 ? o_u : o_v), oy_step, ou_step, nv12 ? ou_step : ov_step};
+    const Planes in = src.in();
+    const PlanesOut out = dst.out();
+    const int crows = rows / 2;
     if ((rc = launch_stats_plane(d, in.y, y_step, g)) != LVK_HIP_OK) return rc;
     {
         const float inv_area_s = g.fast ? 1.0f / (float)((long long)g.iscale * g.iscale) : 0.0f;
@@ -308,8 +265,7 @@ extern "C" int lvk_hip_deblock_apply_yuv420(lvk_hip_deblock* d, const void* d_y,
     const Lin8Entry *sx, *sy;
     if ((rc = blend_tables(ctx, d, true, &kx, &ky, &sx, &sy)) != LVK_HIP_OK) return rc;
     {
-        const int flags = (aligned_to(d_y, y_step, 4) ? kYInDw : 0) | (aligned_to(o_y, oy_step, 4) ? kYOutDw : 0)
-                        | ((nv12 ? aligned_to(o_u, ou_step, 4) : aligned_to(o_u, ou_step, 2) && aligned_to(o_v, ov_step, 2)) ? kChromaWide : 0);
+        const int flags = access_flags(&src, dst);
         const dim3 grid(((cols + 3) / 4 + 63) / 64, (crows + 3) / 4), block(64, 4);
         if (nv12)
             hipLaunchKernelGGL(k_deblock_blend_420<true>, grid, block, 0, ctx->stream, in, out, rows, cols, g.rh, g.rw, (const float*)d->d_keep, g.ex, kx, ky,

@@ -477,9 +477,8 @@ int lvk_get_lin8tab(lvk_hip_ctx* ctx, int ssize, int dsize, bool vertical, const
 int lvk_launch_ingest_yuv420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_y, int y_step, const void* d_u, int u_step,
                              const void* d_v, int v_step, int nv12, int rows, int cols, void* d_dst, int dst_step)
 {
-    LVK_HIP_REQUIRE(ctx, d_y && d_u && (nv12 || d_v) && d_dst && rows > 0 && cols > 0);
-    LVK_HIP_REQUIRE(ctx, (rows & 1) == 0 && (cols & 1) == 0);                       // 4:2:0 needs even dimensions
-    LVK_HIP_REQUIRE(ctx, y_step >= cols && dst_step >= 3 * cols && u_step >= (nv12 ? cols : cols / 2));
+    LVK_HIP_REQUIRE(ctx, yuv420::well_formed(yuv420::plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols)));
+    LVK_HIP_REQUIRE(ctx, d_dst && dst_step >= 3 * cols);
     const Lin8Entry *xt, *yt;
     int rc;
     if ((rc = lvk_get_lin8tab(ctx, cols / 2, cols, false, &xt)) != LVK_HIP_OK) return rc;
@@ -512,9 +511,8 @@ int lvk_launch_ingest_yuv420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d
 int lvk_launch_egress_yuv420(lvk_hip_ctx* ctx, hipStream_t stream, const void* d_src, int src_step, int rows, int cols,
                              void* d_y, int y_step, void* d_u, int u_step, void* d_v, int v_step, int nv12)
 {
-    LVK_HIP_REQUIRE(ctx, d_src && d_y && d_u && (nv12 || d_v) && rows > 0 && cols > 0);
-    LVK_HIP_REQUIRE(ctx, (rows & 1) == 0 && (cols & 1) == 0);
-    LVK_HIP_REQUIRE(ctx, src_step >= 3 * cols && y_step >= cols && u_step >= (nv12 ? cols : cols / 2));
+    LVK_HIP_REQUIRE(ctx, yuv420::well_formed(yuv420::plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols)));
+    LVK_HIP_REQUIRE(ctx, d_src && src_step >= 3 * cols);
     const dim3 block(64, 4), grid((cols / 2 + 63) / 64, (rows / 2 + 3) / 4);
     if (nv12)
         hipLaunchKernelGGL(k_egress_yuv420<true>, grid, block, 0, stream, (const uint8_t*)d_src, src_step, rows, cols, (uint8_t*)d_y, y_step, (uint8_t*)d_u, u_step, (uint8_t*)d_u, u_step);

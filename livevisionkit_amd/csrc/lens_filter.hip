@@ -17,43 +17,14 @@ LVK_REMAP_KERNEL(bool NV12, , k_remap_map_420,
                  (const uint8_t* __restrict__ src, int src_step, int rows, int cols, PlanesOut o, const uint8_t* __restrict__ map, int map_step, uint32_t bg),
 {
     const MapCoord coord{map, map_step};
-    remap_strip<true, W>(src, src_step, rows, cols, Sink420<NV12>{o.y, o.ys, o.u, o.us, o.v, o.vs}, rows, cols, coord, bg);
+    remap_strip<true, W>(src, src_step, rows, cols, sink420<NV12>(o), rows, cols, coord, bg);
 })
 
-// What both 4:2:0 entries ask of the output planes of a rows x cols frame: there, even sizes of at least 2, rows inside their pitches, no two sharing a byte
-int planes_out_ok(lvk_hip_ctx* ctx, const char* name, void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int rows, int cols, int nv12)
-{
-    LVK_HIP_REQUIRE(ctx, o_y && o_u && (nv12 || o_v));
-    LVK_HIP_REQUIRE(ctx, rows >= 2 && cols >= 2 && ((rows | cols) & 1) == 0);                   // 4:2:0 needs even dimensions
-    LVK_HIP_REQUIRE(ctx, remap_plane_ok(o_y, oy_step, rows, cols, 1));
-    LVK_HIP_REQUIRE(ctx, remap_plane_ok(o_u, ou_step, rows / 2, cols / 2, nv12 ? 2 : 1) && (nv12 || remap_plane_ok(o_v, ov_step, rows / 2, cols / 2, 1)));
-    const int crow = nv12 ? cols : cols / 2, n = nv12 ? 2 : 3;
-    const Span out[3] = {span_of(o_y, oy_step, rows, cols), span_of(o_u, ou_step, rows / 2, crow), span_of(nv12 ? o_u : o_v, nv12 ? ou_step : ov_step, rows / 2, crow)};
-    for (int i = 0; i < n; i++)
-        for (int j = i + 1; j < n; j++)
-            if (overlap(out[i], out[j])) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": two output planes overlap");
-    return LVK_HIP_OK;
-}
-
-// ... and of `n_in` input byte ranges against them: the kernels read neighbours, so no input byte may be an output byte
-int inputs_clear_of_outputs(lvk_hip_ctx* ctx, const char* name, const Span* in, int n_in, void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step,
-                            int rows, int cols, int nv12)
-{
-    const int crow = nv12 ? cols : cols / 2, n = nv12 ? 2 : 3;
-    const Span out[3] = {span_of(o_y, oy_step, rows, cols), span_of(o_u, ou_step, rows / 2, crow), span_of(nv12 ? o_u : o_v, nv12 ? ou_step : ov_step, rows / 2, crow)};
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n_in; j++)
-            if (overlap(in[j], out[i])) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": an output plane overlaps an input (the call is out of place)");
-    return LVK_HIP_OK;
-}
-
 // the one launch of the family: every argument has been checked
-int launch_remap_map_420(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step,
-                         int nv12, const void* d_map, int map_step, const uint8_t bg[3])
+int launch_remap_map_420(lvk_hip_ctx* ctx, const void* d_src, int src_step, const PlaneSet& dst, const void* d_map, int map_step, const uint8_t bg[3])
 {
-    const PlanesOut planes{(uint8_t*)o_y, (uint8_t*)o_u, (uint8_t*)(nv12 ? o_u : o_v), oy_step, ou_step, nv12 ? ou_step : ov_step};
-    launch_remap(ctx, LVK_REMAP_FORMS(k_remap_map_420, false, true), nv12 != 0, rows, cols, RemapLaunch{ctx->stream, ctx->remap_precision}, 0,
-                 (const uint8_t*)d_src, src_step, rows, cols, planes, (const uint8_t*)d_map, map_step, pack_bg(bg));
+    launch_remap(ctx, LVK_REMAP_FORMS(k_remap_map_420, false, true), dst.nv12 != 0, dst.rows, dst.cols, RemapLaunch{ctx->stream, ctx->remap_precision}, 0,
+                 (const uint8_t*)d_src, src_step, dst.rows, dst.cols, dst.out(), (const uint8_t*)d_map, map_step, pack_bg(bg));
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
 }
@@ -130,12 +101,13 @@ int lvk_hip_remap_map_yuv420(lvk_hip_ctx* ctx, const void* d_src, int src_step, 
     const char* name = "lvk_hip_remap_map_yuv420";
     LVK_HIP_REQUIRE(ctx, remap_precision_known(ctx->remap_precision));
     LVK_HIP_REQUIRE(ctx, bg != nullptr);
-    int rc = planes_out_ok(ctx, name, o_y, oy_step, o_u, ou_step, o_v, ov_step, rows, cols, nv12);
-    if (rc != LVK_HIP_OK) return rc;
+    const PlaneSet dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols);
+    LVK_HIP_REQUIRE(ctx, well_formed(dst, true));
     LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_src, src_step, rows, cols, 3) && remap_map_ok(d_map, map_step, rows, cols));
     const Span in[2] = {span_of(d_src, src_step, rows, 3 * cols), span_of(d_map, map_step, rows, 8 * cols)};
-    if ((rc = inputs_clear_of_outputs(ctx, name, in, 2, o_y, oy_step, o_u, ou_step, o_v, ov_step, rows, cols, nv12)) != LVK_HIP_OK) return rc;
-    return launch_remap_map_420(ctx, d_src, src_step, rows, cols, o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, d_map, map_step, bg);
+    const int rc = require_out_of_place(ctx, name, in, 2, dst);
+    if (rc != LVK_HIP_OK) return rc;
+    return launch_remap_map_420(ctx, d_src, src_step, dst, d_map, map_step, bg);
 }
 
 int lvk_hip_lens_configure(lvk_hip_lens* lens, const lvk_camera_params* profile, int test_mode)
@@ -243,13 +215,11 @@ int lvk_hip_lens_apply_yuv420(lvk_hip_lens* lens, const void* d_y, int y_step, c
     LVK_HIP_ENTRY(ctx);
     const char* name = "lvk_hip_lens_apply_yuv420";
     LVK_HIP_REQUIRE(ctx, remap_precision_known(ctx->remap_precision));
-    LVK_HIP_REQUIRE(ctx, d_y && d_u && (nv12 || d_v));
-    int rc = planes_out_ok(ctx, name, o_y, oy_step, o_u, ou_step, o_v, ov_step, rows, cols, nv12);
+    const PlaneSet src = plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols), dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols);
+    LVK_HIP_REQUIRE(ctx, well_formed(src) && well_formed(dst, true));
+    const Spans src_spans = spans_of(src);
+    int rc = require_out_of_place(ctx, name, src_spans.s, src_spans.n, dst);
     if (rc != LVK_HIP_OK) return rc;
-    const int crow = nv12 ? cols : cols / 2;                            // bytes of a chroma row
-    LVK_HIP_REQUIRE(ctx, y_step >= cols && u_step >= crow && (nv12 || v_step >= crow));
-    const Span in[3] = {span_of(d_y, y_step, rows, cols), span_of(d_u, u_step, rows / 2, crow), span_of(nv12 ? d_u : d_v, nv12 ? u_step : v_step, rows / 2, crow)};
-    if ((rc = inputs_clear_of_outputs(ctx, name, in, nv12 ? 2 : 3, o_y, oy_step, o_u, ou_step, o_v, ov_step, rows, cols, nv12)) != LVK_HIP_OK) return rc;
     if (lens->selected && (rc = lens->prepare(rows, cols)) != LVK_HIP_OK) return rc;
 
     // The packed source frame comes from the context's pool and goes back to it once the last kernel is enqueued: whoever is handed it next enqueues
@@ -260,7 +230,7 @@ int lvk_hip_lens_apply_yuv420(lvk_hip_lens* lens, const void* d_y, int y_step, c
     rc = lvk_launch_ingest_yuv420(ctx, ctx->stream, d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols, d_packed, p_step);
     if (rc == LVK_HIP_OK && lens->test_mode) rc = lvk_launch_draw_grid(ctx, ctx->stream, d_packed, p_step, rows, cols, kGridW, kGridH, kMagentaYUV, 1);
     if (rc == LVK_HIP_OK)
-        rc = lens->selected ? launch_remap_map_420(ctx, d_packed, p_step, rows, cols, o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, lens->d_map, lens->map_step(), kBackground)
+        rc = lens->selected ? launch_remap_map_420(ctx, d_packed, p_step, dst, lens->d_map, lens->map_step(), kBackground)
                             : lvk_launch_egress_yuv420(ctx, ctx->stream, d_packed, p_step, rows, cols, o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12);
     (void)lvk_hip_free(ctx, d_packed);
     return rc;

@@ -13,6 +13,7 @@
 #include <utility>
 
 #include "lvk_hip.h"
+#include "planes420.hpp"
 
 struct LinTabEntry { int s0, s1; float a0, a1; };   // one column/row of the INTER_LINEAR mesh->frame table
 struct Lin8Entry { int s0, s1, a0, a1; };            // 8-bit INTER_LINEAR table entry: two source indices, 11-bit coefficients
@@ -189,9 +190,7 @@ inline int lvk_format_channels(int format)
 // neighbours must not write over its source (in place included)
 inline bool lvk_pitched_overlap(const void* a, int a_step, int a_rows, long long a_row_bytes, const void* b, int b_step, int b_rows, long long b_row_bytes)
 {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)((long long)(a_rows - 1) * a_step + a_row_bytes);
-    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)((long long)(b_rows - 1) * b_step + b_row_bytes);
-    return a0 < b1 && b0 < a1;
+    return yuv420::overlap(yuv420::span_of(a, a_step, a_rows, a_row_bytes), yuv420::span_of(b, b_step, b_rows, b_row_bytes));
 }
 
 // Copies `bytes` (<= kStageBytes) of host data into a device staging slot, asynchronously on the

@@ -66,8 +66,9 @@ void k_easu_scale(const uint8_t* __restrict__ src, int src_step, int src_rows, i
 
 // ---- remap + 4:2:0 egress in one kernel (lvk_hip_stab_push_yuv420): YUV frames only, same size in and out, occupancy-capped like
 //      the other kernels the overlap mode runs next to the tracker
-struct Planes420 { uint8_t* y; int y_step; uint8_t* u; int u_step; uint8_t* v; int v_step; };
-template <bool NV12> __device__ __forceinline__ Sink420<NV12> sink420(const Planes420& o) { return Sink420<NV12>{o.y, o.y_step, o.u, o.u_step, o.v, o.v_step}; }
+//      Planes420: yuv420::PlanesOut in the order these sixteen kernels have always taken their planes in.  It stays: with PlanesOut as the argument the
+//      compiler groups the scalar argument loads differently and every one of them comes out with another instruction stream.
+struct Planes420 { uint8_t* y; int ys; uint8_t* u; int us; uint8_t* v; int vs; };
 
 LVK_REMAP_KERNEL(bool NV12, LVK_CO_SCHEDULED, k_remap_homography_420,
                  (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Planes420 o, HomographyArgs H, uint32_t bg),
@@ -191,10 +192,10 @@ int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, const void* d_src, int src_s
 {
     LVK_HIP_REQUIRE(ctx, remap_precision_known(o.precision));
     LVK_HIP_REQUIRE(ctx, bg != nullptr && remap_mesh_ok(mesh, mesh_rows, mesh_cols));
-    LVK_HIP_REQUIRE(ctx, (rows & 1) == 0 && (cols & 1) == 0 && remap_plane_ok(d_src, src_step, rows, cols, 3) && remap_plane_ok(o_y, oy_step, rows, cols, 1));
-    // the chroma planes: cols / 2 samples of one byte each (I420) or of a U V pair (NV12)
-    LVK_HIP_REQUIRE(ctx, remap_plane_ok(o_u, ou_step, rows / 2, cols / 2, nv12 ? 2 : 1) && (nv12 || remap_plane_ok(o_v, ov_step, rows / 2, cols / 2, 1)));
-    const Planes420 planes{(uint8_t*)o_y, oy_step, (uint8_t*)o_u, ou_step, (uint8_t*)(nv12 ? o_u : o_v), nv12 ? ou_step : ov_step};
+    const yuv420::PlaneSet dst = yuv420::plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols);
+    LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_src, src_step, rows, cols, 3) && yuv420::well_formed(dst, true));
+    const yuv420::PlanesOut po = dst.out();
+    const Planes420 planes{po.y, po.ys, po.u, po.us, po.v, po.vs};
     const size_t lds_pad = o.co_scheduled ? (size_t)LVK_CO_LDS_PAD : 0;          // A / B switch (scripts/variant_build.sh): unused LDS that caps the persistent grid's blocks per CU
     if (mesh_rows == 2 && mesh_cols == 2)
     {

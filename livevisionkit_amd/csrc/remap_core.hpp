@@ -560,6 +560,9 @@ struct Sink420
     }
 };
 
+// the sink of the 4:2:0 kernels, from the planes they take as their argument: yuv420::PlanesOut, or remap.hip's Planes420 of the same members
+template <bool NV12, class P> __device__ __forceinline__ Sink420<NV12> sink420(const P& o) { return Sink420<NV12>{o.y, o.ys, o.u, o.us, o.v, o.vs}; }
+
 template <bool YUV, class W = EasuExact, class Coord, class Sink>
 __device__ __forceinline__ void remap_one_strip(const uint8_t* __restrict__ src, int src_step, int src_rows, int src_cols,
                                                 const Sink& sink, int dst_rows, int dst_cols, const Coord& coord, uint32_t bg,
@@ -696,9 +699,8 @@ inline void launch_remap(const lvk_hip_ctx* ctx, const RemapForms<K>& forms, boo
 // ---- argument rules shared by the launchers, once each ------------------------------------------------------------------------------------------
 inline bool remap_precision_known(int precision) { return precision == LVK_REMAP_EXACT || precision == LVK_REMAP_1LSB; }
 
-// The kernels address a frame with ONE 32-bit byte offset per pixel built from 24-bit factors (easu_gather, the sinks): the whole frame
-// must lie within 4 GB of its base and rows / pitch below 2^24 (an 8K packed frame is 100 MB with a 23 KB pitch).
-inline bool fits_u32(int step, int rows) { return step > 0 && rows > 0 && step < (1 << 24) && rows < (1 << 24) && (uint64_t)step * (uint64_t)rows < (1ull << 32); }
+// The kernels address a frame with ONE 32-bit byte offset per pixel built from 24-bit factors (easu_gather, the sinks): planes420.hpp has the rule
+using yuv420::fits_u32;
 
 // a plane of rows x cols pixels of `bpp` bytes, `step` bytes apart, as every kernel needs it: there, not empty, rows inside the pitch, addressable
 inline bool remap_plane_ok(const void* p, int step, int rows, int cols, int bpp)

@@ -22,8 +22,6 @@ using namespace yuv420;
 namespace {
 
 constexpr int ROWS = 4;                                   // rows per thread, as lvk_launch_sharpen chose them
-// flags of k_rcas_420: which of the wide accesses the planes' bases and pitches allow
-constexpr int kYInDw = 1, kYOutDw = 2, kChromaWide = 4;
 
 // Rows of a packed 8UC3 frame, loaded as k_rcas loads them.  The last thread of a row with cols % 4 == 2 has no 12 bytes of its own: it reads its six
 // pixels one by one, columns clamped into the row.
@@ -145,7 +143,7 @@ void k_rcas_420(Src src, PlanesOut out, int rows, int cols, float sharp, int fla
     const int x0 = (int)blockIdx.x * RCAS_STRIP_W + (int)(threadIdx.x & 63) * RCAS_PXT;
     const int y0 = ((int)blockIdx.y * 4 + (int)(threadIdx.x >> 6)) * ROWS;
     if (x0 >= cols || y0 >= rows) return;
-    const bool four = x0 + RCAS_PXT <= cols;                // else the row's last two columns
+    const bool half = x0 + RCAS_PXT > cols;                 // the row's last two columns
 
     typename Src::Raw raw;                                  // rows y0 - 1 .. y0 + ROWS, all in flight together
     src.load(raw, x0, y0, rows, cols, flags);
@@ -175,13 +173,7 @@ void k_rcas_420(Src src, PlanesOut out, int rows, int cols, float sharp, int fla
             o[p] = border ? centre[p] : px;
         }
         // luma out
-        uint8_t* py = out.y + (size_t)y * out.ys + x0;
-        if (four && (flags & kYOutDw)) *reinterpret_cast<uint32_t*>(py) = (o[0] & 0xffu) | ((o[1] & 0xffu) << 8) | ((o[2] & 0xffu) << 16) | (o[3] << 24);
-        else
-        {
-            py[0] = (uint8_t)o[0]; py[1] = (uint8_t)o[1];
-            if (four) { py[2] = (uint8_t)o[2]; py[3] = (uint8_t)o[3]; }
-        }
+        store_luma4(out.y + (size_t)y * out.ys + x0, o, half, flags);
         if (!(r & 1))
         {
 #pragma unroll
@@ -200,29 +192,17 @@ void k_rcas_420(Src src, PlanesOut out, int rows, int cols, float sharp, int fla
         }
         if constexpr (NV12)
         {
+            // (written out: through store_chroma2<true> this kernel's dword store comes out with the sources of one v_bitop3_b32 commuted, and the
+            //  kernels' instruction streams are kept as they were -- DESIGN.md section 28)
             uint8_t* p = out.u + (size_t)k * out.us + 2 * c0;
-            if (four && (flags & kChromaWide)) *reinterpret_cast<uint32_t*>(p) = u[0] | (v[0] << 8) | (u[1] << 16) | (v[1] << 24);
+            if (!half && (flags & kChromaWide)) *reinterpret_cast<uint32_t*>(p) = u[0] | (v[0] << 8) | (u[1] << 16) | (v[1] << 24);
             else
             {
                 p[0] = (uint8_t)u[0]; p[1] = (uint8_t)v[0];
-                if (four) { p[2] = (uint8_t)u[1]; p[3] = (uint8_t)v[1]; }
+                if (!half) { p[2] = (uint8_t)u[1]; p[3] = (uint8_t)v[1]; }
             }
         }
-        else
-        {
-            uint8_t* pu = out.u + (size_t)k * out.us + c0;
-            uint8_t* pv = out.v + (size_t)k * out.vs + c0;
-            if (four && (flags & kChromaWide))
-            {
-                *reinterpret_cast<uint16_t*>(pu) = (uint16_t)(u[0] | (u[1] << 8));
-                *reinterpret_cast<uint16_t*>(pv) = (uint16_t)(v[0] | (v[1] << 8));
-            }
-            else
-            {
-                pu[0] = (uint8_t)u[0]; pv[0] = (uint8_t)v[0];
-                if (four) { pu[1] = (uint8_t)u[1]; pv[1] = (uint8_t)v[1]; }
-            }
-        }
+        else store_chroma2<false>(out, k, c0, u, v, half, flags);
     }
 }
 
@@ -243,56 +223,39 @@ extern "C" int lvk_hip_scale_yuv420(lvk_hip_ctx* ctx,
                                     int nv12, float sharpness)
 {
     LVK_HIP_ENTRY(ctx);
-    const std::string name("lvk_hip_scale_yuv420");
-    LVK_HIP_REQUIRE(ctx, d_y && d_u && (nv12 || d_v) && o_y && o_u && (nv12 || o_v));
-    LVK_HIP_REQUIRE(ctx, src_rows >= 2 && src_cols >= 2 && dst_rows >= 2 && dst_cols >= 2);
-    LVK_HIP_REQUIRE(ctx, ((src_rows | src_cols | dst_rows | dst_cols) & 1) == 0);            // 4:2:0 needs even dimensions
+    const PlaneSet src = plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, src_rows, src_cols);
+    const PlaneSet dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, dst_rows, dst_cols);
+    LVK_HIP_REQUIRE(ctx, well_formed(src) && well_formed(dst));
     LVK_HIP_REQUIRE(ctx, dst_cols >= src_cols && dst_rows >= src_rows);                      // Image.cpp:157
     LVK_HIP_REQUIRE(ctx, sharpness >= 0.0f && sharpness <= 1.0f);                            // LVK_ASSERT_01, Image.cpp:210 (a NaN fails both)
-    const int scrow = nv12 ? src_cols : src_cols / 2, dcrow = nv12 ? dst_cols : dst_cols / 2;    // bytes of a chroma row
-    LVK_HIP_REQUIRE(ctx, y_step >= src_cols && u_step >= scrow && (nv12 || v_step >= scrow));
-    LVK_HIP_REQUIRE(ctx, oy_step >= dst_cols && ou_step >= dcrow && (nv12 || ov_step >= dcrow));
-    {
-        // out of place: the sharpening and the chroma up-sampling read their neighbours, so no input byte may be an output byte, and no output byte another's
-        const int n = nv12 ? 2 : 3;
-        const Span in[3] = {span_of(d_y, y_step, src_rows, src_cols), span_of(d_u, u_step, src_rows / 2, scrow),
-                            span_of(nv12 ? d_u : d_v, nv12 ? u_step : v_step, src_rows / 2, scrow)};
-        const Span out[3] = {span_of(o_y, oy_step, dst_rows, dst_cols), span_of(o_u, ou_step, dst_rows / 2, dcrow),
-                             span_of(nv12 ? o_u : o_v, nv12 ? ou_step : ov_step, dst_rows / 2, dcrow)};
-        for (int i = 0; i < n; i++)
-        {
-            for (int j = 0; j < n; j++)
-                if (overlap(in[j], out[i])) return ctx->fail(LVK_HIP_ERR_ARG, name + ": an output plane overlaps an input plane (the call is out of place)");
-            for (int j = i + 1; j < n; j++)
-                if (overlap(out[i], out[j])) return ctx->fail(LVK_HIP_ERR_ARG, name + ": two output planes overlap");
-        }
-    }
+    int rc;
+    // out of place: the sharpening and the chroma up-sampling read their neighbours
+    const Spans src_spans = spans_of(src);
+    if ((rc = require_out_of_place(ctx, "lvk_hip_scale_yuv420", src_spans.s, src_spans.n, dst)) != LVK_HIP_OK) return rc;
     const float sharp = exp2f(-2.0f * (1.0f - sharpness));                                   // Image.cpp:227
-    const PlanesOut out{(uint8_t*)o_y, (uint8_t*)o_u, (uint8_t*)(nv12 ? o_u : o_v), oy_step, ou_step, nv12 ? ou_step : ov_step};
-    const int out_flags = (aligned_to(o_y, oy_step, 4) ? kYOutDw : 0)
-                        | ((nv12 ? aligned_to(o_u, ou_step, 4) : aligned_to(o_u, ou_step, 2) && aligned_to(o_v, ov_step, 2)) ? kChromaWide : 0);
+    const PlanesOut out = dst.out();
 
     if (dst_rows == src_rows && dst_cols == src_cols)       // lvk::upscale copies (Image.cpp:162-166): the sharpening reads the planes itself
     {
-        const Planes in{(const uint8_t*)d_y, (const uint8_t*)d_u, (const uint8_t*)(nv12 ? d_u : d_v), y_step, u_step, nv12 ? u_step : v_step};
-        const int flags = out_flags | (aligned_to(d_y, y_step, 4) ? kYInDw : 0);
+        const Planes in = src.in();
+        const int flags = access_flags(&src, dst);
         return nv12 ? launch_rcas_420<PlanarSrc<true>, true>(ctx, PlanarSrc<true>{in}, out, dst_rows, dst_cols, sharp, flags)
                     : launch_rcas_420<PlanarSrc<false>, false>(ctx, PlanarSrc<false>{in}, out, dst_rows, dst_cols, sharp, flags);
     }
+    const int out_flags = access_flags(nullptr, dst);
 
     // The two packed frames between the three launches come from the context's pool and go back to it once the last kernel is enqueued: whoever is
     // handed them next enqueues behind that kernel on this context's stream (lvk_hip.h, lvk_hip_free), and the steady state allocates nothing.
     const int s_step = (3 * src_cols + 3) & ~3, p_step = (3 * dst_cols + 3) & ~3;
     void *d_small = nullptr, *d_big = nullptr;
-    int rc;
     if ((rc = lvk_hip_malloc(ctx, (size_t)s_step * src_rows, &d_small)) != LVK_HIP_OK) return rc;
     if ((rc = lvk_hip_malloc(ctx, (size_t)p_step * dst_rows, &d_big)) == LVK_HIP_OK
         && (rc = lvk_launch_ingest_yuv420(ctx, ctx->stream, d_y, y_step, d_u, u_step, d_v, v_step, nv12, src_rows, src_cols, d_small, s_step)) == LVK_HIP_OK
         && (rc = lvk_launch_upscale(ctx, ctx->stream, d_small, s_step, src_rows, src_cols, d_big, p_step, dst_rows, dst_cols, 1)) == LVK_HIP_OK)
     {
-        const PackedSrc src{(const uint8_t*)d_big, p_step};
-        rc = nv12 ? launch_rcas_420<PackedSrc, true>(ctx, src, out, dst_rows, dst_cols, sharp, out_flags)
-                  : launch_rcas_420<PackedSrc, false>(ctx, src, out, dst_rows, dst_cols, sharp, out_flags);
+        const PackedSrc big{(const uint8_t*)d_big, p_step};
+        rc = nv12 ? launch_rcas_420<PackedSrc, true>(ctx, big, out, dst_rows, dst_cols, sharp, out_flags)
+                  : launch_rcas_420<PackedSrc, false>(ctx, big, out, dst_rows, dst_cols, sharp, out_flags);
     }
     (void)lvk_hip_free(ctx, d_small);
     (void)lvk_hip_free(ctx, d_big);

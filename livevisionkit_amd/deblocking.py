@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 
 from . import _native
+from .context import _planes420_args, _planes420_empty
 from .stabilization import FORMAT_YUV, frame_args
 
 _c = ctypes
@@ -66,13 +67,10 @@ class DeblockingFilter:
         call (lvk_hip_deblock_apply_yuv420): byte for byte the ingest -> apply(FORMAT_YUV) -> egress chain.  `out` = the output planes in the same
         layout (allocated when None; rows may be padded: stride(-1) == 1, NV12 UV stride(1) == 2).  Returns (planes, region); asynchronous on the
         context's stream."""
-        import torch
         nv12 = v is None
         planes = (y, u) if nv12 else (y, u, v)
-        if out is None:
-            out = tuple(torch.empty_like(p, memory_format=torch.contiguous_format) for p in planes)
-        out = tuple(out)
         rows, cols = int(y.shape[0]), int(y.shape[1])
+        out = _planes420_empty(rows, cols, nv12, y.device) if out is None else tuple(out)
         if len(out) != len(planes):
             raise ValueError("`out` holds one plane per input plane")
         chroma = (rows // 2, cols // 2, 2) if nv12 else (rows // 2, cols // 2)
@@ -81,14 +79,8 @@ class DeblockingFilter:
             if tuple(p.shape) != shape or p.dtype.itemsize != 1 or p.stride(-1) != 1 or (p.dim() == 3 and p.stride(1) != 2):
                 raise ValueError("8-bit planes [rows, cols], [rows/2, cols/2] (NV12: [rows/2, cols/2, 2]) with contiguous rows are required")
 
-        def args(ps):
-            a = []
-            for p in ps:
-                a += [p.data_ptr(), p.stride(0)]
-            return a + ([None, 0] if nv12 else [])
-
         region = (_c.c_int * 4)()
-        self.ctx._check(self.lib.lvk_hip_deblock_apply_yuv420(self.handle, *args(planes), *args(out), 1 if nv12 else 0, rows, cols, region))
+        self.ctx._check(self.lib.lvk_hip_deblock_apply_yuv420(self.handle, *_planes420_args(planes, nv12), *_planes420_args(out, nv12), 1 if nv12 else 0, rows, cols, region))
         return out, tuple(region)
 
     def draw_influence(self, frame, fmt=FORMAT_YUV):

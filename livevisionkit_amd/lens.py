@@ -6,7 +6,7 @@ is drawn before the warp.  Frames are torch uint8 tensors on the GPU with contig
 and out of place."""
 import ctypes
 
-from .context import Context
+from .context import Context, _planes420_args, _planes420_empty
 from .stabilization import CHANNELS, FORMAT_BGRA, FORMAT_GRAY, FORMAT_YUV, frame_args, gray_frame_args, out_frame
 
 _c = ctypes
@@ -70,23 +70,13 @@ class LCFilter:
         """The planes of an I420 (y [rows, cols], u, v [rows/2, cols/2]) or NV12 (v=None, u [rows/2, cols/2, 2]) frame in one call
         (lvk_hip_lens_apply_yuv420): byte for byte ingest_yuv420 -> [draw_grid] -> remap_map(yuv=True, bg 0) -> egress_yuv420.  `out` = the output
         planes in the same layout (allocated when None).  Returns them."""
-        import torch
         nv12 = v is None
         planes = (y, u) if nv12 else (y, u, v)
-        if out is None:
-            out = tuple(torch.empty_like(p, memory_format=torch.contiguous_format) for p in planes)
-        out = tuple(out)
+        rows, cols = int(y.shape[0]), int(y.shape[1])
+        out = _planes420_empty(rows, cols, nv12, y.device) if out is None else tuple(out)
         if len(out) != len(planes):
             raise ValueError("`out` holds one plane per input plane")
-        rows, cols = int(y.shape[0]), int(y.shape[1])
-
-        def args(ps):
-            a = []
-            for p in ps:
-                a += [p.data_ptr(), p.stride(0)]
-            return a + ([None, 0] if nv12 else [])
-
-        self.ctx._check(self.lib.lvk_hip_lens_apply_yuv420(self.handle, *args(planes), *args(out), rows, cols, 1 if nv12 else 0))
+        self.ctx._check(self.lib.lvk_hip_lens_apply_yuv420(self.handle, *_planes420_args(planes, nv12), *_planes420_args(out, nv12), rows, cols, 1 if nv12 else 0))
         return out
 
     def close(self):

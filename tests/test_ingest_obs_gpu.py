@@ -124,6 +124,58 @@ def test_refusals(ctx):
     assert ctx.obs_frame_format("UYVY") == 4 and ctx.obs_frame_format("Y800") == 5 and ctx.obs_frame_format("RGBA") == 2 and ctx.obs_frame_format("BGRX") == 0
 
 
+@pytest.mark.parametrize("way", ["ingest", "egress"])
+def test_yuv420_refuses_a_v_pitch_below_its_row(ctx, oracle, way):
+    """lvk_hip_ingest_yuv420 / lvk_hip_egress_yuv420 on an 8 x 8 I420 frame whose v_step is cols / 2 - 1: LVK_HIP_ERR_ARG like every other 4:2:0
+    entry, nothing launched (the destination keeps its bytes), and the next valid call is bit-exact.  NV12 has no V plane: nv12 = 1 with
+    v_step = 0 is accepted as before."""
+    import torch
+    rows, cols, ERR_ARG = 8, 8, -1
+    y, u, v = _planes(oracle, "I420", rows, cols, seed=5)
+    frame = oracle.ingest_obs("I420", [y, u, v])
+    gy, gu, gv, gframe = _gpu(y), _gpu(u), _gpu(v), _gpu(frame)
+    lib, h = ctx.lib, ctx.handle
+    if way == "ingest":
+        dst = torch.full((rows, cols, 3), 0xA5, dtype=torch.uint8, device="cuda")
+
+        def call(vp, v_step, nv12, up=gu):
+            return lib.lvk_hip_ingest_yuv420(h, gy.data_ptr(), gy.stride(0), up.data_ptr(), up.stride(0), vp, v_step, nv12, rows, cols, dst.data_ptr(), dst.stride(0))
+
+        assert call(gv.data_ptr(), cols // 2 - 1, 0) == ERR_ARG
+        ctx.sync()
+        assert (dst == 0xA5).all()
+        assert call(gv.data_ptr(), gv.stride(0), 0) == 0
+        ctx.sync()
+        assert np.array_equal(dst.cpu().numpy(), frame)
+        uv = np.stack([u, v], axis=-1)
+        guv = _gpu(uv)
+        assert call(None, 0, 1, up=guv) == 0
+        ctx.sync()
+        assert np.array_equal(dst.cpu().numpy(), oracle.ingest_obs("NV12", [y, uv]))
+    else:
+        want = oracle.egress_obs("I420", frame)
+        out = [torch.full(p.shape, 0xA5, dtype=torch.uint8, device="cuda") for p in (y, u, v)]
+
+        def call(planes, v_step, nv12):
+            vp = planes[2].data_ptr() if len(planes) > 2 else None
+            return lib.lvk_hip_egress_yuv420(h, gframe.data_ptr(), gframe.stride(0), rows, cols, planes[0].data_ptr(), planes[0].stride(0),
+                                             planes[1].data_ptr(), planes[1].stride(0), vp, v_step, nv12)
+
+        assert call(out, cols // 2 - 1, 0) == ERR_ARG
+        ctx.sync()
+        assert all((p == 0xA5).all() for p in out)
+        assert call(out, out[2].stride(0), 0) == 0
+        ctx.sync()
+        for p, w in zip(out, want):
+            assert np.array_equal(p.cpu().numpy(), w)
+        want12 = oracle.egress_obs("NV12", frame)
+        out12 = [torch.full(p.shape, 0xA5, dtype=torch.uint8, device="cuda") for p in want12]
+        assert call(out12, 0, 1) == 0
+        ctx.sync()
+        for p, w in zip(out12, want12):
+            assert np.array_equal(p.cpu().numpy(), w)
+
+
 def test_stabilizer_fed_from_packed_422(ctx, oracle):
     """A UYVY stream (what a capture card delivers) through ingest -> lvk_hip_stab_push -> egress equals the oracle's stabilizer fed the oracle's frames."""
     import livevisionkit_amd as lvk
