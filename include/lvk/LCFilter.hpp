@@ -1,7 +1,8 @@
 // lvk::LCFilter of the C++ facade: the OBS plugin's lens-correction filter (Modules/OBS-Plugin/Sources/Enhancement/LCFilter.cpp:99-192) over the
 // lvk_hip_lens_* object of lvk_hip.h.  The plugin runs it on OBS frames; here it is a VideoFilter, so it chains in
 // CompositeFilter (correct the lens, then stabilize) and takes the frames FrameIngest::upload_obs_frame makes -- BGR / RGB / YUV, BGRA / RGBA and
-// GRAY -- and, through apply(VideoFrame420, VideoFrame420), the I420 / NV12 planes of the asynchronous path in one call.
+// GRAY -- and, through apply(VideoFrame420, VideoFrame420), the I420 / NV12 planes of the asynchronous path in one call; through
+// apply(VideoFrameOBS, VideoFrameOBS) the planes of every OBS video format.
 // Included by LiveVisionKit.hpp.
 #pragma once
 
@@ -60,6 +61,28 @@ public:
                                                    output.y(), output.y_step(), output.u(), output.uv_step(), output.v(), output.uv_step(),
                                                    input.rows, input.cols, input.nv12 ? 1 : 0),
                          "LCFilter::apply(4:2:0)");
+        });
+        sync_gpu(profile); frame_timer().stop();
+    }
+
+    // The plugin's LCFilter::filter(OBSFrame&) for a frame of ANY OBS video format in one call (lvk_hip_lens_apply_obs): byte for byte
+    // FrameIngest::to_ocl -> filter -> FrameIngest::to_obs.  Out of place: `output` is created at the input's size, format and context (bytes to_obs
+    // leaves alone -- the last quarter of an RGBA / BGRA / BGRX plane -- are whatever the fresh block held); the input planes are not written.
+    // A Y800 frame is refused in test mode.
+    void apply(const VideoFrameOBS& input, VideoFrameOBS& output, const bool profile = false)
+    {
+        LVK_HIP_ASSERT(!input.empty());
+        LVK_HIP_ASSERT(&input != &output);
+        LVK_HIP_ASSERT(input.format != LVK_VIDEO_FORMAT_Y800 || !m_Settings.test_mode);
+        ensure(input.context());
+        sync_gpu(profile); frame_timer().start();
+        output.create({input.cols, input.rows}, input.format, input.context());
+        LVK_HIP_ASSERT(output.data[0] != input.data[0]);
+        output.timestamp = input.timestamp;
+        run(input.context(), [&] {
+            m_Ctx->check(lvk_hip_lens_apply_obs(m_Handle, input.format, reinterpret_cast<const void* const*>(input.data), input.linesize,
+                                                reinterpret_cast<void* const*>(output.data), output.linesize, input.rows, input.cols),
+                         "LCFilter::apply(OBS)");
         });
         sync_gpu(profile); frame_timer().stop();
     }

@@ -387,6 +387,68 @@ private:
     size_t m_bytes = 0;
 };
 
+// The device twin of HostFrameOBS: one frame of any OBS video format FrameIngest::Select accepts -- Y800 included -- in one lvk_hip_malloc block, planes
+// tightly packed one after the other as plane_table lays them out.  LCFilter::apply takes it directly (lvk_hip_lens_apply_obs).
+struct VideoFrameOBS
+{
+    uint64_t timestamp = 0;
+    int format = 0;                                   // LVK_VIDEO_FORMAT_* = libobs' enum video_format
+    int cols = 0, rows = 0;
+    uint8_t* data[3] = {nullptr, nullptr, nullptr};
+    int linesize[3] = {0, 0, 0};
+
+    static int plane_table(int format, int rows, int cols, int prow[3], int pbytes[3])
+    {
+        if (format != LVK_VIDEO_FORMAT_Y800) return HostFrameOBS::plane_table(format, rows, cols, prow, pbytes);
+        prow[0] = rows; pbytes[0] = cols;
+        return 1;
+    }
+
+    bool empty() const { return !m_buf || cols == 0 || rows == 0; }
+    void release() { m_buf.reset(); cols = rows = 0; for (int i = 0; i < 3; i++) { data[i] = nullptr; linesize[i] = 0; } }
+    void create(const cv::Size& sz, int obs_format, const std::shared_ptr<hip::Context>& ctx = nullptr)
+    {
+        int prow[3] = {0, 0, 0}, pbytes[3] = {0, 0, 0};
+        const int n = plane_table(obs_format, sz.height, sz.width, prow, pbytes);
+        LVK_HIP_ASSERT(n > 0 && sz.width > 0 && sz.height > 0);
+        if (m_buf && m_buf.use_count() == 1 && cols == sz.width && rows == sz.height && format == obs_format && (!ctx || ctx == m_ctx)) return;
+        m_ctx = ctx ? ctx : (m_ctx ? m_ctx : hip::shared_context());
+        size_t total = 0;
+        for (int i = 0; i < n; i++) total += (size_t)prow[i] * pbytes[i];
+        void* p = nullptr;
+        m_ctx->check(lvk_hip_malloc(m_ctx->get(), total, &p), "VideoFrameOBS::create");
+        auto c = m_ctx;
+        m_buf = std::shared_ptr<void>(p, [c](void* q) { lvk_hip_free(c->get(), q); });
+        cols = sz.width; rows = sz.height; format = obs_format; m_bytes = total;
+        uint8_t* q = static_cast<uint8_t*>(p);
+        for (int i = 0; i < 3; i++)
+        {
+            data[i] = i < n ? q : nullptr; linesize[i] = i < n ? pbytes[i] : 0;
+            if (i < n) q += (size_t)prow[i] * pbytes[i];
+        }
+    }
+    size_t bytes() const { return m_bytes; }
+    // host: the planes one after the other, bytes() bytes
+    void upload(const uint8_t* host, int rows_, int cols_, int obs_format, uint64_t ts, const std::shared_ptr<hip::Context>& ctx = nullptr)
+    {
+        create({cols_, rows_}, obs_format, ctx);
+        hip::ContextLock lock(m_ctx->mutex());
+        m_ctx->check(lvk_hip_upload(m_ctx->get(), m_buf.get(), host, m_bytes), "VideoFrameOBS::upload");
+        timestamp = ts;
+    }
+    void download(uint8_t* host) const
+    {
+        hip::ContextLock lock(m_ctx->mutex());
+        m_ctx->check(lvk_hip_download(m_ctx->get(), host, m_buf.get(), m_bytes), "VideoFrameOBS::download");
+        m_ctx->check(lvk_hip_sync(m_ctx->get()), "VideoFrameOBS::download");
+    }
+    const std::shared_ptr<hip::Context>& context() const { return m_ctx; }
+private:
+    std::shared_ptr<void> m_buf;
+    std::shared_ptr<hip::Context> m_ctx;
+    size_t m_bytes = 0;
+};
+
 // ---------------------------------------------------------------------------------------------- Timing
 class Time
 {

@@ -911,6 +911,30 @@ int  lvk_hip_lens_apply_c4(lvk_hip_lens* lens, const void* d_src, int src_step, 
 int  lvk_hip_lens_apply_yuv420(lvk_hip_lens* lens, const void* d_y, int y_step, const void* d_u, int u_step, const void* d_v, int v_step,
                                void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int rows, int cols, int nv12);
 
+/* ---- the same for EVERY video format FrameIngest::Select accepts ------------------------------------------------------------------
+ * lvk_hip_remap_map_obs: the primitive.  d_src a packed YUV 8UC3 frame, d_map as for lvk_hip_remap_map_yuv420, o_planes / o_steps the planes of
+ * `video_format` as lvk_hip_egress_obs takes them: byte for byte lvk_hip_remap_map(.., yuv = 1) followed by lvk_hip_egress_obs, in one kernel, in the
+ * context's remap precision.  It takes I422 / I42A, YUY2 / YVYU / UYVY, I444 / YUVA and AYUV (an AYUV plane may start at any byte); I420 / I40A / NV12 go
+ * through lvk_hip_remap_map_yuv420; every other format is LVK_HIP_ERR_ARG.
+ * lvk_hip_lens_apply_obs: the filter, planes in (d_planes / steps as for lvk_hip_ingest_obs), planes of the same format out.  Byte for byte
+ *     lvk_hip_ingest_obs -> [test mode: lvk_hip_draw_grid, 32 x 32, col::MAGENTA of lvk_hip_obs_frame_format(video_format), thickness 1]
+ *     -> [profile selected: lvk_hip_remap_map(yuv = the frame format is LVK_FORMAT_YUV, bg 0 0 0)] -> lvk_hip_egress_obs
+ * in the context's remap precision; without a profile ingest -> [grid] -> egress (the chroma of a subsampled format is the resampled chroma, as in the
+ * plugin).  Bytes lvk_hip_egress_obs leaves alone stay the caller's: pitch padding, the alpha planes of I40A / I42A / YUVA (no arguments here), and the
+ * last quarter of data[0] of RGBA / BGRA / BGRX, whose DirectIngest moves rows * cols * 3 bytes -- reproduced, not endorsed, as above.  The input planes
+ * are never written, in test mode either.  Y800 is a one-channel frame: lvk_hip_lens_apply_gray plane to plane, refused in test mode like it.  The
+ * packed frame between the steps is a block of the context's pool that returns to it inside the call.  The handle is left as the packed apply of that
+ * frame size leaves it, so the call alternates freely with every other lvk_hip_lens_apply*.
+ * Both refuse with LVK_HIP_ERR_ARG, nothing written or enqueued: a NULL lens, d_planes, steps, o_planes or o_steps; what lvk_hip_ingest_obs refuses of
+ * the input planes; an output plane that is NULL where the format uses it or whose pitch is below its row; odd cols on 4:2:2, odd rows or cols on 4:2:0;
+ * rows or cols below 2 with a profile selected; steps[0] != 4 * cols on RGBA / BGRA / BGRX, in or out; a plane too large for the kernels' 32-bit
+ * offsets; an input plane (the source, the map) overlapping an output plane, two output planes overlapping; Y800 in test mode; an unknown format; and --
+ * the one refusal the chain has that the fused kernel has not -- an AYUV output plane or pitch that is no multiple of 4 while no profile is selected. */
+int  lvk_hip_remap_map_obs(lvk_hip_ctx* ctx, int video_format, const void* d_src, int src_step, int rows, int cols,
+                           void* const o_planes[3], const int o_steps[3], const void* d_map, int map_step, const uint8_t bg[3]);
+int  lvk_hip_lens_apply_obs(lvk_hip_lens* lens, int video_format, const void* const d_planes[3], const int steps[3],
+                            void* const o_planes[3], const int o_steps[3], int rows, int cols);
+
 #ifdef __cplusplus
 }
 #endif

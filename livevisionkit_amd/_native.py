@@ -182,6 +182,8 @@ _SIG = {
     "lvk_hip_lens_apply_c4": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int]),
     "lvk_hip_lens_apply_yuv420": (_c.c_int, [_P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int,
                                              _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_remap_map_obs": (_c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P * 3, _c.c_int * 3, _P, _c.c_int, _c.POINTER(_c.c_uint8)]),
+    "lvk_hip_lens_apply_obs": (_c.c_int, [_P, _c.c_int, _P * 3, _c.c_int * 3, _P * 3, _c.c_int * 3, _c.c_int, _c.c_int]),
 }
 
 # what include/lvk_hip_deblock_px.h declares (lvk_hip.h includes it; the header has its own pin, tests/test_deblock_px_spec.py)

@@ -414,6 +414,20 @@ class Context:
                                                       offsets.data_ptr(), offsets.stride(0) * 4, bgp))
         return out
 
+    def video_format(self, fmt):
+        """The LVK_VIDEO_FORMAT_* number of `fmt`, a name of VIDEO_FORMATS or the number itself."""
+        return self.VIDEO_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+
+    def remap_map_obs(self, fmt, src, offset_map, planes, bg=(0, 0, 0)):
+        """lvk_hip_remap_map_obs: remap_map(yuv=True) + egress_obs(fmt) in one kernel: packed YUV [rows, cols, 3] and offsets [rows, cols, 2] into the
+        given planes of `fmt` (a name or a number; I422 / I42A, YUY2 / YVYU / UYVY, I444 / YUVA, AYUV, and I420 / I40A / NV12).  Returns `planes`."""
+        rows, cols = src.shape[0], src.shape[1]
+        ptrs, steps = self._obs_args(planes)
+        bga, bgp = _u8x3(bg)
+        self._check(self.lib.lvk_hip_remap_map_obs(self.handle, self.video_format(fmt), src.data_ptr(), src.stride(0), rows, cols, ptrs, steps,
+                                                   offset_map.data_ptr(), offset_map.stride(0) * 4, bgp))
+        return planes
+
     def upscale(self, src, size, yuv=True, out=None):
         """lvk::upscale(src, dst, size, yuv): EASU upsampling to size = (width, height) >= the source size."""
         import torch

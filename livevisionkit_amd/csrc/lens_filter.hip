@@ -3,6 +3,9 @@
 // (lvk_hip_remap_map_yuv420), the counterpart of k_remap_mesh_420 for MapCoord.  Everything the kernel is made of is in remap_core.hpp: remap_strip<true, W>
 // with MapCoord and Sink420<NV12>, defined through LVK_REMAP_KERNEL so that the exact kernel and its 1-LSB twin share one body.
 //
+// lvk_hip_remap_map_obs / lvk_hip_lens_apply_obs take the planes of every other OBS video format: their kernels are the sinks of
+// remap_obs.hip behind lvk_launch_remap_map_obs, and the conversions of ingest.hip; this unit adds routing and checks for them, no kernel.
+//
 // The object owns what the plugin's filter owns: the camera profile, the offset map of the last frame size (lvk_lens_build_offsets of lens.hip, rebuilt
 // when the size or the profile changed) and the test-mode grid, which is drawn BEFORE the warp so that it is warped with the frame.
 #include "remap_core.hpp"
@@ -89,6 +92,90 @@ int copy_frame(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int 
     return LVK_HIP_OK;
 }
 
+// lvk_hip_remap_map_yuv420 behind its entry guard: also the I420 / I40A / NV12 route of lvk_hip_remap_map_obs
+int remap_map_420(lvk_hip_ctx* ctx, const char* name, const void* d_src, int src_step, const PlaneSet& dst, const void* d_map, int map_step, const uint8_t bg[3])
+{
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(ctx->remap_precision));
+    LVK_HIP_REQUIRE(ctx, bg != nullptr);
+    LVK_HIP_REQUIRE(ctx, well_formed(dst, true));
+    LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_src, src_step, dst.rows, dst.cols, 3) && remap_map_ok(d_map, map_step, dst.rows, dst.cols));
+    const Span in[2] = {span_of(d_src, src_step, dst.rows, 3 * dst.cols), span_of(d_map, map_step, dst.rows, 8 * dst.cols)};
+    const int rc = require_out_of_place(ctx, name, in, 2, dst);
+    if (rc != LVK_HIP_OK) return rc;
+    return launch_remap_map_420(ctx, d_src, src_step, dst, d_map, map_step, bg);
+}
+
+// lvk_hip_lens_apply_yuv420 behind its entry guard: also the I420 / I40A / NV12 route of lvk_hip_lens_apply_obs
+int apply_420(lvk_hip_lens* lens, const char* name, const PlaneSet& src, const PlaneSet& dst)
+{
+    lvk_hip_ctx* ctx = lens->ctx;
+    const int rows = dst.rows, cols = dst.cols;
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(ctx->remap_precision));
+    LVK_HIP_REQUIRE(ctx, well_formed(src) && well_formed(dst, true));
+    const Spans src_spans = spans_of(src);
+    int rc = require_out_of_place(ctx, name, src_spans.s, src_spans.n, dst);
+    if (rc != LVK_HIP_OK) return rc;
+    if (lens->selected && (rc = lens->prepare(rows, cols)) != LVK_HIP_OK) return rc;
+
+    // The packed source frame comes from the context's pool and goes back to it once the last kernel is enqueued: whoever is handed it next enqueues
+    // behind that kernel on this context's stream (lvk_hip.h, lvk_hip_free), and the steady state allocates nothing.
+    const int p_step = (3 * cols + 3) & ~3;
+    void* d_packed = nullptr;
+    if ((rc = lvk_hip_malloc(ctx, (size_t)p_step * rows, &d_packed)) != LVK_HIP_OK) return rc;
+    const Planes in = src.in();
+    const PlanesOut out = dst.out();
+    rc = lvk_launch_ingest_yuv420(ctx, ctx->stream, in.y, in.ys, in.u, in.us, in.v, in.vs, src.nv12, rows, cols, d_packed, p_step);
+    if (rc == LVK_HIP_OK && lens->test_mode) rc = lvk_launch_draw_grid(ctx, ctx->stream, d_packed, p_step, rows, cols, kGridW, kGridH, kMagentaYUV, 1);
+    if (rc == LVK_HIP_OK)
+        rc = lens->selected ? launch_remap_map_420(ctx, d_packed, p_step, dst, lens->d_map, lens->map_step(), kBackground)
+                            : lvk_launch_egress_yuv420(ctx, ctx->stream, d_packed, p_step, rows, cols, out.y, out.ys, out.u, out.us, out.v, out.vs, dst.nv12);
+    (void)lvk_hip_free(ctx, d_packed);
+    return rc;
+}
+
+// ---- the OBS video formats that are not 4:2:0 (lvk_hip_remap_map_obs, lvk_hip_lens_apply_obs) --------------------------------------------------------
+bool is_420(int vf) { return vf == LVK_VIDEO_FORMAT_I420 || vf == LVK_VIDEO_FORMAT_I40A || vf == LVK_VIDEO_FORMAT_NV12; }
+PlaneSet plane_set_420(int vf, const void* const p[3], const int s[3], int rows, int cols)
+{
+    return plane_set(p[0], s[0], p[1], s[1], p[2], s[2], vf == LVK_VIDEO_FORMAT_NV12 ? 1 : 0, rows, cols);
+}
+
+// The planes FrameIngest moves for one rows x cols frame of a format outside 4:2:0: their number and the bytes of a row (every plane has `rows` rows).
+// The 4-byte DirectIngest formats are the tight plane of 4 * cols bytes a row of which rows * cols * 3 bytes move.  0 planes: no such format.
+struct ObsRows { int n; int bytes[3]; };
+ObsRows obs_rows(int vf, int cols)
+{
+    switch (vf)
+    {
+    case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A: return {3, {cols, cols / 2, cols / 2}};
+    case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA: return {3, {cols, cols, cols}};
+    case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: case LVK_VIDEO_FORMAT_UYVY: return {1, {2 * cols, 0, 0}};
+    case LVK_VIDEO_FORMAT_AYUV: case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX: return {1, {4 * cols, 0, 0}};
+    case LVK_VIDEO_FORMAT_BGR3: return {1, {3 * cols, 0, 0}};
+    case LVK_VIDEO_FORMAT_Y800: return {1, {cols, 0, 0}};
+    default: return {0, {0, 0, 0}};
+    }
+}
+bool is_direct4(int vf) { return vf == LVK_VIDEO_FORMAT_RGBA || vf == LVK_VIDEO_FORMAT_BGRA || vf == LVK_VIDEO_FORMAT_BGRX; }
+
+// The output planes of one frame (cols even on 4:2:2: the caller has checked): every plane there, its row inside its pitch, addressable by the sinks; clear
+// of the `n_in` input spans and of one another
+int obs_outputs_ok(lvk_hip_ctx* ctx, const char* name, int vf, void* const o_planes[3], const int o_steps[3], int rows, int cols, const Span* in, int n_in)
+{
+    const ObsRows t = obs_rows(vf, cols);
+    if (t.n == 0) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": video format " + std::to_string(vf) + " is not one FrameIngest::Select knows");
+    Spans out{{}, t.n};
+    for (int i = 0; i < t.n; i++)
+    {
+        LVK_HIP_REQUIRE(ctx, remap_plane_ok(o_planes[i], o_steps[i], rows, t.bytes[i], 1));
+        out.s[i] = span_of(o_planes[i], o_steps[i], rows, t.bytes[i]);
+    }
+    LVK_HIP_REQUIRE(ctx, !is_direct4(vf) || o_steps[0] == 4 * cols);
+    if (!clear_of(in, n_in, out)) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": an output plane overlaps an input (the call is out of place)");
+    if (!disjoint(out)) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": two output planes overlap");
+    return LVK_HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -98,16 +185,26 @@ int lvk_hip_remap_map_yuv420(lvk_hip_ctx* ctx, const void* d_src, int src_step, 
                              const void* d_map, int map_step, const uint8_t bg[3])
 {
     LVK_HIP_ENTRY(ctx);
-    const char* name = "lvk_hip_remap_map_yuv420";
+    return remap_map_420(ctx, "lvk_hip_remap_map_yuv420", d_src, src_step, plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols), d_map, map_step, bg);
+}
+
+int lvk_hip_remap_map_obs(lvk_hip_ctx* ctx, int video_format, const void* d_src, int src_step, int rows, int cols,
+                          void* const o_planes[3], const int o_steps[3], const void* d_map, int map_step, const uint8_t bg[3])
+{
+    LVK_HIP_ENTRY(ctx);
+    const char* name = "lvk_hip_remap_map_obs";
+    LVK_HIP_REQUIRE(ctx, o_planes != nullptr && o_steps != nullptr);
+    if (is_420(video_format)) return remap_map_420(ctx, name, d_src, src_step, plane_set_420(video_format, o_planes, o_steps, rows, cols), d_map, map_step, bg);
+    if (!lvk_remap_obs_fusable(video_format)) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": no fused sink for video format " + std::to_string(video_format));
     LVK_HIP_REQUIRE(ctx, remap_precision_known(ctx->remap_precision));
     LVK_HIP_REQUIRE(ctx, bg != nullptr);
-    const PlaneSet dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols);
-    LVK_HIP_REQUIRE(ctx, well_formed(dst, true));
     LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_src, src_step, rows, cols, 3) && remap_map_ok(d_map, map_step, rows, cols));
+    const bool full_chroma = video_format == LVK_VIDEO_FORMAT_I444 || video_format == LVK_VIDEO_FORMAT_YUVA || video_format == LVK_VIDEO_FORMAT_AYUV;
+    LVK_HIP_REQUIRE(ctx, full_chroma || (cols & 1) == 0);                          // 4:2:2 has an even width
     const Span in[2] = {span_of(d_src, src_step, rows, 3 * cols), span_of(d_map, map_step, rows, 8 * cols)};
-    const int rc = require_out_of_place(ctx, name, in, 2, dst);
+    const int rc = obs_outputs_ok(ctx, name, video_format, o_planes, o_steps, rows, cols, in, 2);
     if (rc != LVK_HIP_OK) return rc;
-    return launch_remap_map_420(ctx, d_src, src_step, dst, d_map, map_step, bg);
+    return lvk_launch_remap_map_obs(ctx, video_format, d_src, src_step, rows, cols, o_planes, o_steps, d_map, map_step, bg, RemapLaunch{ctx->stream, ctx->remap_precision});
 }
 
 int lvk_hip_lens_configure(lvk_hip_lens* lens, const lvk_camera_params* profile, int test_mode)
@@ -213,25 +310,78 @@ int lvk_hip_lens_apply_yuv420(lvk_hip_lens* lens, const void* d_y, int y_step, c
     if (!lens) return LVK_HIP_ERR_ARG;
     lvk_hip_ctx* ctx = lens->ctx;
     LVK_HIP_ENTRY(ctx);
-    const char* name = "lvk_hip_lens_apply_yuv420";
-    LVK_HIP_REQUIRE(ctx, remap_precision_known(ctx->remap_precision));
-    const PlaneSet src = plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols), dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols);
-    LVK_HIP_REQUIRE(ctx, well_formed(src) && well_formed(dst, true));
-    const Spans src_spans = spans_of(src);
-    int rc = require_out_of_place(ctx, name, src_spans.s, src_spans.n, dst);
-    if (rc != LVK_HIP_OK) return rc;
-    if (lens->selected && (rc = lens->prepare(rows, cols)) != LVK_HIP_OK) return rc;
+    return apply_420(lens, "lvk_hip_lens_apply_yuv420", plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols),
+                     plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols));
+}
 
-    // The packed source frame comes from the context's pool and goes back to it once the last kernel is enqueued: whoever is handed it next enqueues
-    // behind that kernel on this context's stream (lvk_hip.h, lvk_hip_free), and the steady state allocates nothing.
+int lvk_hip_lens_apply_obs(lvk_hip_lens* lens, int video_format, const void* const d_planes[3], const int steps[3],
+                           void* const o_planes[3], const int o_steps[3], int rows, int cols)
+{
+    if (!lens) return LVK_HIP_ERR_ARG;
+    lvk_hip_ctx* ctx = lens->ctx;
+    LVK_HIP_ENTRY(ctx);
+    const char* name = "lvk_hip_lens_apply_obs";
+    const int vf = video_format;
+    LVK_HIP_REQUIRE(ctx, d_planes != nullptr && steps != nullptr && o_planes != nullptr && o_steps != nullptr);
+    if (is_420(vf)) return apply_420(lens, name, plane_set_420(vf, d_planes, steps, rows, cols), plane_set_420(vf, o_planes, o_steps, rows, cols));
+
+    // ---- everything that can refuse the call, before anything is enqueued
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(ctx->remap_precision));
+    int rc = lvk_ingest_obs_check(ctx, vf, d_planes, steps, rows, cols);          // the planes in use, their pitches, the parity of the size, the format
+    if (rc != LVK_HIP_OK) return rc;
+    if (vf == LVK_VIDEO_FORMAT_Y800 && lens->test_mode) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": the test-mode grid draws three bytes per pixel (Y800)");
+    LVK_HIP_REQUIRE(ctx, !lens->selected || (rows > 1 && cols > 1));
+    const ObsRows t = obs_rows(vf, cols);
+    Span in[3];
+    for (int i = 0; i < t.n; i++)
+    {
+        LVK_HIP_REQUIRE(ctx, remap_plane_ok(d_planes[i], steps[i], rows, t.bytes[i], 1));
+        in[i] = span_of(d_planes[i], steps[i], rows, t.bytes[i]);
+    }
+    if ((rc = obs_outputs_ok(ctx, name, vf, o_planes, o_steps, rows, cols, in, t.n)) != LVK_HIP_OK) return rc;
+    // (without a profile an AYUV frame leaves through lvk_launch_egress_obs, which stores dwords: refused here as lvk_hip_egress_obs refuses it there)
+    if (vf == LVK_VIDEO_FORMAT_AYUV && !lens->selected && !aligned_to(o_planes[0], o_steps[0], 4))
+        return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": without a profile the AYUV output plane and its pitch are multiples of 4 (lvk_hip_egress_obs)");
+    if (lens->selected && (rc = lens->prepare(rows, cols)) != LVK_HIP_OK) return rc;
+    const RemapLaunch launch{ctx->stream, ctx->remap_precision};
+
+    if (vf == LVK_VIDEO_FORMAT_Y800)                                              // a one-channel frame, plane to plane (lvk_hip_lens_apply_gray)
+        return lens->selected ? lvk_launch_remap_map_gray(ctx, d_planes[0], steps[0], rows, cols, o_planes[0], o_steps[0], lens->d_map, lens->map_step(), kBackground[0], launch)
+                              : copy_frame(ctx, d_planes[0], steps[0], rows, cols, o_planes[0], o_steps[0], 1);
+
+    // the packed frame of the ingest: a block of the context's pool that goes back once the last kernel is enqueued (apply_420)
     const int p_step = (3 * cols + 3) & ~3;
     void* d_packed = nullptr;
+
+    if (!lvk_remap_obs_fusable(vf))
+    {
+        // BGR3 and the DirectIngest formats ARE packed three-byte frames -- BGR3 at its own pitch, RGBA / BGRA / BGRX the first rows * cols * 3 bytes of the
+        // tight plane, a frame of pitch 3 * cols (lvk_ingest_obs_check) --, so ingest and egress are copies and the remap runs plane to plane.  Only the
+        // grid needs a frame of its own: the input planes are never written.
+        const bool bgr3 = vf == LVK_VIDEO_FORMAT_BGR3;
+        const void* src = d_planes[0];
+        int src_step = bgr3 ? steps[0] : 3 * cols;
+        const int dst_step = bgr3 ? o_steps[0] : 3 * cols;
+        if (lens->test_mode)
+        {
+            if ((rc = lvk_hip_malloc(ctx, (size_t)p_step * rows, &d_packed)) != LVK_HIP_OK) return rc;
+            rc = lvk_launch_ingest_obs(ctx, ctx->stream, vf, d_planes, steps, rows, cols, d_packed, p_step);
+            if (rc == LVK_HIP_OK) rc = lvk_launch_draw_grid(ctx, ctx->stream, d_packed, p_step, rows, cols, kGridW, kGridH, kMagentaBGR, 1);
+            src = d_packed; src_step = p_step;
+        }
+        if (rc == LVK_HIP_OK)
+            rc = lens->selected ? lvk_launch_remap_map(ctx, src, src_step, rows, cols, o_planes[0], dst_step, lens->d_map, lens->map_step(), kBackground, 0, launch)
+                                : copy_frame(ctx, src, src_step, rows, cols, o_planes[0], dst_step, 3);
+        if (d_packed) (void)lvk_hip_free(ctx, d_packed);
+        return rc;
+    }
+
     if ((rc = lvk_hip_malloc(ctx, (size_t)p_step * rows, &d_packed)) != LVK_HIP_OK) return rc;
-    rc = lvk_launch_ingest_yuv420(ctx, ctx->stream, d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols, d_packed, p_step);
+    rc = lvk_launch_ingest_obs(ctx, ctx->stream, vf, d_planes, steps, rows, cols, d_packed, p_step);
     if (rc == LVK_HIP_OK && lens->test_mode) rc = lvk_launch_draw_grid(ctx, ctx->stream, d_packed, p_step, rows, cols, kGridW, kGridH, kMagentaYUV, 1);
     if (rc == LVK_HIP_OK)
-        rc = lens->selected ? launch_remap_map_420(ctx, d_packed, p_step, dst, lens->d_map, lens->map_step(), kBackground)
-                            : lvk_launch_egress_yuv420(ctx, ctx->stream, d_packed, p_step, rows, cols, o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12);
+        rc = lens->selected ? lvk_launch_remap_map_obs(ctx, vf, d_packed, p_step, rows, cols, o_planes, o_steps, lens->d_map, lens->map_step(), kBackground, launch)
+                            : lvk_launch_egress_obs(ctx, ctx->stream, vf, d_packed, p_step, rows, cols, o_planes, o_steps);
     (void)lvk_hip_free(ctx, d_packed);
     return rc;
 }

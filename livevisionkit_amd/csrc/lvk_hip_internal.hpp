@@ -441,3 +441,6 @@ int lvk_launch_warpmesh_apply_420(lvk_hip_ctx* ctx, const void* d_src, int src_s
 bool lvk_remap_obs_fusable(int video_format);
 int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, int video_format, const void* d_src, int src_step, int rows, int cols,
                                   void* const planes[3], const int steps[3], const float* mesh, int mesh_rows, int mesh_cols, const uint8_t bg[3], const RemapLaunch& o);
+// remap by a materialised offset map + the egress of a format lvk_remap_obs_fusable names in one kernel (remap_obs.hip); no lens, full grid
+int lvk_launch_remap_map_obs(lvk_hip_ctx* ctx, int video_format, const void* d_src, int src_step, int rows, int cols,
+                             void* const planes[3], const int steps[3], const void* d_map, int map_step, const uint8_t bg[3], const RemapLaunch& o);

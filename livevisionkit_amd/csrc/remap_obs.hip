@@ -2,7 +2,8 @@
 // writes the frame the way FrameIngest::to_obs would (reference: Modules/OBS-Plugin/Interop/FrameIngest.cpp:526-557 I4XXIngest, :640-666 P422Ingest,
 // :690-703 P444Ingest) -- planar or packed 4:2:2 (chroma = cv::resize(0.5, 1.0, INTER_AREA) = the pixel pair's mean, round half to even), planar 4:4:4,
 // AYUV.  Same bytes as lvk_launch_warpmesh_apply_lens followed by lvk_launch_egress_obs (tests/test_ingest_obs_gpu.py holds the two routes together);
-// what it saves is the packed intermediate (2 x 3 W H bytes), one kernel and one launch per frame.
+// what it saves is the packed intermediate (2 x 3 W H bytes), one kernel and one launch per frame.  The same sinks behind a materialised offset map
+// (k_remap_map_planes, lvk_launch_remap_map_obs) are the lens filter's remap + egress on these formats: lvk_hip_remap_map_obs, DESIGN.md section 29.
 #include "remap_core.hpp"
 
 namespace {
@@ -112,6 +113,13 @@ LVK_REMAP_KERNEL(class Sink, LVK_CO_SCHEDULED, k_remap_mesh_lens_planes,
     LVK_WITH_MESH_COORD(true, L, rows, cols, (remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, coord, bg)))
 })
 
+// Full grid only, as k_remap_map_420: a materialised map has no persistent-grid form (lvk_launch_remap_map)
+LVK_REMAP_KERNEL(class Sink, , k_remap_map_planes,
+                 (const uint8_t* __restrict__ src, int src_step, int rows, int cols, Sink sink, const uint8_t* __restrict__ map, int map_step, uint32_t bg),
+{
+    remap_strip<true, W>(src, src_step, rows, cols, sink, rows, cols, MapCoord{map, map_step}, bg);
+})
+
 // (the family's "flag" is the sink type: one form per precision)
 template <class Sink>
 int launch_planes(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, int cols, const Sink& sink,
@@ -134,6 +142,37 @@ int launch_planes(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows, i
     });
 }
 
+// The sink of `video_format` over the caller's planes, checked, handed to launch(sink): the one switch of the two launchers below.  Plane i holds
+// rows x `c` samples of `bpp` bytes; 4:2:2 has an even width.
+template <class Launch>
+int with_obs_sink(lvk_hip_ctx* ctx, const char* who, int video_format, int rows, int cols, void* const planes[3], const int steps[3], const Launch& launch)
+{
+    uint8_t* p0 = (uint8_t*)planes[0]; uint8_t* p1 = (uint8_t*)planes[1]; uint8_t* p2 = (uint8_t*)planes[2];
+    auto plane_ok = [&](int i, int c, int bpp) { return remap_plane_ok(planes[i], steps[i], rows, c, bpp); };
+    switch (video_format)
+    {
+    case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A:
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 1) && plane_ok(1, cols / 2, 1) && plane_ok(2, cols / 2, 1));
+        return launch(Sink422<0>{p0, steps[0], p1, steps[1], p2, steps[2]});
+    case LVK_VIDEO_FORMAT_YUY2:
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
+        return launch(Sink422<1>{p0, steps[0], p0, 0, p0, 0});
+    case LVK_VIDEO_FORMAT_YVYU:
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
+        return launch(Sink422<2>{p0, steps[0], p0, 0, p0, 0});
+    case LVK_VIDEO_FORMAT_UYVY:
+        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
+        return launch(Sink422<3>{p0, steps[0], p0, 0, p0, 0});
+    case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA:
+        LVK_HIP_REQUIRE(ctx, plane_ok(0, cols, 1) && plane_ok(1, cols, 1) && plane_ok(2, cols, 1));
+        return launch(Sink444<0>{p0, steps[0], p1, steps[1], p2, steps[2]});
+    case LVK_VIDEO_FORMAT_AYUV:
+        LVK_HIP_REQUIRE(ctx, plane_ok(0, cols, 4));
+        return launch(Sink444<1>{p0, steps[0], p0, 0, p0, 0});
+    }
+    return ctx->fail(LVK_HIP_ERR_ARG, std::string(who) + ": no fused sink for video format " + std::to_string(video_format));
+}
+
 } // namespace
 
 bool lvk_remap_obs_fusable(int video_format)
@@ -152,29 +191,22 @@ int lvk_launch_warpmesh_apply_obs(lvk_hip_ctx* ctx, int video_format, const void
 {
     LVK_HIP_REQUIRE(ctx, remap_precision_known(o.precision));
     LVK_HIP_REQUIRE(ctx, planes && steps && bg && remap_mesh_ok(mesh, mesh_rows, mesh_cols) && remap_plane_ok(d_src, src_step, rows, cols, 3));
-    uint8_t* p0 = (uint8_t*)planes[0]; uint8_t* p1 = (uint8_t*)planes[1]; uint8_t* p2 = (uint8_t*)planes[2];
-    // plane i holds rows x `c` samples of `bpp` bytes
-    auto plane_ok = [&](int i, int c, int bpp) { return remap_plane_ok(planes[i], steps[i], rows, c, bpp); };
-    switch (video_format)
-    {
-    case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 1) && plane_ok(1, cols / 2, 1) && plane_ok(2, cols / 2, 1));
-        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, o);
-    case LVK_VIDEO_FORMAT_YUY2:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
-        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
-    case LVK_VIDEO_FORMAT_YVYU:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
-        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<2>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
-    case LVK_VIDEO_FORMAT_UYVY:
-        LVK_HIP_REQUIRE(ctx, (cols & 1) == 0 && plane_ok(0, cols, 2));
-        return launch_planes(ctx, d_src, src_step, rows, cols, Sink422<3>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
-    case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA:
-        LVK_HIP_REQUIRE(ctx, plane_ok(0, cols, 1) && plane_ok(1, cols, 1) && plane_ok(2, cols, 1));
-        return launch_planes(ctx, d_src, src_step, rows, cols, Sink444<0>{p0, steps[0], p1, steps[1], p2, steps[2]}, mesh, mesh_rows, mesh_cols, bg, o);
-    case LVK_VIDEO_FORMAT_AYUV:
-        LVK_HIP_REQUIRE(ctx, plane_ok(0, cols, 4));
-        return launch_planes(ctx, d_src, src_step, rows, cols, Sink444<1>{p0, steps[0], p0, 0, p0, 0}, mesh, mesh_rows, mesh_cols, bg, o);
-    }
-    return ctx->fail(LVK_HIP_ERR_ARG, "lvk_launch_warpmesh_apply_obs: no fused sink for video format " + std::to_string(video_format));
+    return with_obs_sink(ctx, "lvk_launch_warpmesh_apply_obs", video_format, rows, cols, planes, steps,
+                         [&](const auto& sink) { return launch_planes(ctx, d_src, src_step, rows, cols, sink, mesh, mesh_rows, mesh_cols, bg, o); });
+}
+
+// lvk::remap(offset map) + FrameIngest::to_obs of `video_format` in one kernel: d_src packed YUV 8UC3, d_map rows x cols float2.  Of `o` the stream and
+// the precision are read (lvk_launch_remap_map).  The caller has checked that no output plane overlaps the source, the map or another output plane.
+int lvk_launch_remap_map_obs(lvk_hip_ctx* ctx, int video_format, const void* d_src, int src_step, int rows, int cols,
+                             void* const planes[3], const int steps[3], const void* d_map, int map_step, const uint8_t bg[3], const RemapLaunch& o)
+{
+    LVK_HIP_REQUIRE(ctx, remap_precision_known(o.precision));
+    LVK_HIP_REQUIRE(ctx, planes && steps && bg && remap_map_ok(d_map, map_step, rows, cols) && remap_plane_ok(d_src, src_step, rows, cols, 3));
+    return with_obs_sink(ctx, "lvk_launch_remap_map_obs", video_format, rows, cols, planes, steps, [&](const auto& sink) {
+        using Sink = std::decay_t<decltype(sink)>;
+        launch_remap(ctx, LVK_REMAP_FORMS(k_remap_map_planes, Sink, Sink), false, rows, cols, RemapLaunch{o.stream, o.precision}, 0,
+                     (const uint8_t*)d_src, src_step, rows, cols, sink, (const uint8_t*)d_map, map_step, pack_bg(bg));
+        LVK_HIP_CHECK(ctx, hipGetLastError());
+        return (int)LVK_HIP_OK;
+    });
 }

@@ -3,7 +3,7 @@ DESIGN.md section 27.
 
 The filter owns the camera profile (fx, fy, cx, cy, k1, k2, p1, p2, k3), the offset map of the last frame size and the test mode, whose 32 x 32 magenta grid
 is drawn before the warp.  Frames are torch uint8 tensors on the GPU with contiguous rows (any row pitch); applies are asynchronous on the context's stream
-and out of place."""
+and out of place.  apply_obs takes the planes of any OBS video format in one call (lvk_hip_lens_apply_obs)."""
 import ctypes
 
 from .context import Context, _planes420_args, _planes420_empty
@@ -77,6 +77,28 @@ class LCFilter:
         if len(out) != len(planes):
             raise ValueError("`out` holds one plane per input plane")
         self.ctx._check(self.lib.lvk_hip_lens_apply_yuv420(self.handle, *_planes420_args(planes, nv12), *_planes420_args(out, nv12), rows, cols, 1 if nv12 else 0))
+        return out
+
+    @staticmethod
+    def obs_plane_shapes(fmt, rows, cols):
+        """The planes of one rows x cols frame of `fmt` (a name): StabilizationFilter.obs_plane_shapes, and the one plane of Y800."""
+        from .stabilization import StabilizationFilter
+        return [(rows, cols)] if fmt == "Y800" else StabilizationFilter.obs_plane_shapes(fmt, rows, cols)
+
+    def apply_obs(self, fmt, planes, out=None):
+        """The planes of one frame of ANY OBS video format in one call (lvk_hip_lens_apply_obs): byte for byte ingest_obs -> [draw_grid] ->
+        [remap_map(bg 0)] -> egress_obs.  `fmt` = a name of Context.VIDEO_FORMATS or its number; `planes` as Context.ingest_obs takes them, in the shapes
+        of obs_plane_shapes; `out` = planes of the same shapes (allocated when None: bytes the egress leaves alone are then undefined).  Returns `out`.
+        Y800 is refused in test mode."""
+        import torch
+        planes = list(planes)
+        rows, cols = int(planes[0].shape[0]), int(planes[0].shape[1])
+        out = [torch.empty(tuple(p.shape), dtype=torch.uint8, device=p.device) for p in planes] if out is None else list(out)
+        if len(out) != len(planes):
+            raise ValueError("`out` holds one plane per input plane")
+        iptr, istep = self.ctx._obs_args(planes)
+        optr, ostep = self.ctx._obs_args(out)
+        self.ctx._check(self.lib.lvk_hip_lens_apply_obs(self.handle, self.ctx.video_format(fmt), iptr, istep, optr, ostep, rows, cols))
         return out
 
     def close(self):
