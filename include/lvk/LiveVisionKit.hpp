@@ -1205,6 +1205,35 @@ public:
         });
         sync_gpu(profile); frame_timer().stop();
     }
+
+    // A frame of ANY OBS video format in one call (lvk_hip_scale_obs), byte for byte FrameIngest::to_ocl -> apply(frame, frame) -> FrameIngest::to_obs
+    // without the packed frames between them.  Out of place: `output` is created at output_size in the input's format and context (bytes to_obs leaves
+    // alone -- the last quarter of an RGBA / BGRA / BGRX plane -- are whatever the fresh block held); the input planes are not written.  output_size has
+    // the format's parity and is no smaller than the input; yuv_input says what the format's frame is (a Y800 frame has no YUV form: not looked at).
+    void apply(const VideoFrameOBS& input, VideoFrameOBS& output, const bool profile = false)
+    {
+        LVK_HIP_ASSERT(!input.empty());
+        LVK_HIP_ASSERT(&input != &output);
+        const cv::Size size = m_Settings.output_size;
+        const int vf = input.format;
+        const bool f420 = vf == LVK_VIDEO_FORMAT_I420 || vf == LVK_VIDEO_FORMAT_I40A || vf == LVK_VIDEO_FORMAT_NV12;
+        const bool f422 = vf == LVK_VIDEO_FORMAT_I422 || vf == LVK_VIDEO_FORMAT_I42A || vf == LVK_VIDEO_FORMAT_YUY2 || vf == LVK_VIDEO_FORMAT_YVYU || vf == LVK_VIDEO_FORMAT_UYVY;
+        LVK_HIP_ASSERT(size.width >= input.cols && size.height >= input.rows);
+        LVK_HIP_ASSERT(!(f420 || f422) || size.width % 2 == 0);
+        LVK_HIP_ASSERT(!f420 || size.height % 2 == 0);
+        LVK_HIP_ASSERT(vf == LVK_VIDEO_FORMAT_Y800 || m_Settings.yuv_input == (lvk_hip_obs_frame_format(vf) == LVK_FORMAT_YUV));
+        m_Ctx = input.context();
+        sync_gpu(profile); frame_timer().start();
+        output.create(size, vf, input.context());
+        LVK_HIP_ASSERT(output.data[0] != input.data[0]);
+        output.timestamp = input.timestamp;
+        run(input.context(), [&] {
+            m_Ctx->check(lvk_hip_scale_obs(m_Ctx->get(), vf, reinterpret_cast<const void* const*>(input.data), input.linesize, input.rows, input.cols,
+                                           reinterpret_cast<void* const*>(output.data), output.linesize, output.rows, output.cols, m_Settings.sharpness),
+                         "ScalingFilter::apply(OBS)");
+        });
+        sync_gpu(profile); frame_timer().stop();
+    }
 private:
     void filter(VideoFrame&& input, VideoFrame& output) override
     {

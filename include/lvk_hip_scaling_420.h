@@ -34,4 +34,6 @@ int lvk_hip_scale_yuv420(lvk_hip_ctx* ctx,
 }
 #endif
 
+#include "lvk_hip_scaling_obs.h"  /* lvk_hip_scale_obs: the same filter on every OBS video format (PART 2) */
+
 #endif /* LVK_HIP_SCALING_420_H */

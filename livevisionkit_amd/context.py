@@ -460,6 +460,27 @@ class Context:
                                                   h, w, 1 if nv12 else 0, float(sharpness)))
         return out
 
+    def scale_obs(self, fmt, planes, size=None, sharpness=0.8, out=None):
+        """lvk_hip_scale_obs: lvk::ScalingFilter on the planes of one frame of ANY OBS video format in one call, out of place: the planes of
+        ingest_obs -> upscale(size, yuv = the frame format is YUV) -> sharpen(sharpness) -> egress_obs (Y800: upscale_gray -> sharpen_gray).  `fmt` = a name
+        of VIDEO_FORMATS or its number; `planes` as ingest_obs takes them; size = (width, height) >= the input's, with the format's parity; None: the
+        input's (sharpen only).  `out` = the planes of the output frame (allocated when None -- every plane of a format has the frame's size or half of
+        it, so plane i is the input's plane i at the new size; bytes the egress leaves alone are then undefined).  Returns `out`."""
+        import torch
+        planes = list(planes)
+        rows, cols = int(planes[0].shape[0]), int(planes[0].shape[1])
+        w, h = (cols, rows) if size is None else (int(size[0]), int(size[1]))
+        if out is None:
+            out = [torch.empty((p.shape[0] * h // rows, p.shape[1] * w // cols, *p.shape[2:]), dtype=torch.uint8, device=p.device) for p in planes]
+        else:
+            out = list(out)
+        if len(out) != len(planes):
+            raise ValueError("`out` holds one plane per input plane")
+        iptr, istep = self._obs_args(planes)
+        optr, ostep = self._obs_args(out)
+        self._check(self.lib.lvk_hip_scale_obs(self.handle, self.video_format(fmt), iptr, istep, rows, cols, optr, ostep, h, w, float(sharpness)))
+        return out
+
     # ---- ScalingFilter's two steps on one-channel ([rows, cols]) and four-channel ([rows, cols, 4]; 4-byte aligned, pitches multiples of 4) frames ----
     def _px_upscale(self, sfx, src, size, out):
         out = self._px_out(sfx, src, out, (int(size[1]), int(size[0])))

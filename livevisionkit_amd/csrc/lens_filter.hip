@@ -10,6 +10,7 @@
 // when the size or the profile changed) and the test-mode grid, which is drawn BEFORE the warp so that it is warped with the frame.
 #include "remap_core.hpp"
 #include "yuv420_core.hpp"
+#include "obs_sinks.hpp"
 
 using namespace yuv420;
 
@@ -133,48 +134,8 @@ int apply_420(lvk_hip_lens* lens, const char* name, const PlaneSet& src, const P
     return rc;
 }
 
-// ---- the OBS video formats that are not 4:2:0 (lvk_hip_remap_map_obs, lvk_hip_lens_apply_obs) --------------------------------------------------------
-bool is_420(int vf) { return vf == LVK_VIDEO_FORMAT_I420 || vf == LVK_VIDEO_FORMAT_I40A || vf == LVK_VIDEO_FORMAT_NV12; }
-PlaneSet plane_set_420(int vf, const void* const p[3], const int s[3], int rows, int cols)
-{
-    return plane_set(p[0], s[0], p[1], s[1], p[2], s[2], vf == LVK_VIDEO_FORMAT_NV12 ? 1 : 0, rows, cols);
-}
-
-// The planes FrameIngest moves for one rows x cols frame of a format outside 4:2:0: their number and the bytes of a row (every plane has `rows` rows).
-// The 4-byte DirectIngest formats are the tight plane of 4 * cols bytes a row of which rows * cols * 3 bytes move.  0 planes: no such format.
-struct ObsRows { int n; int bytes[3]; };
-ObsRows obs_rows(int vf, int cols)
-{
-    switch (vf)
-    {
-    case LVK_VIDEO_FORMAT_I422: case LVK_VIDEO_FORMAT_I42A: return {3, {cols, cols / 2, cols / 2}};
-    case LVK_VIDEO_FORMAT_I444: case LVK_VIDEO_FORMAT_YUVA: return {3, {cols, cols, cols}};
-    case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: case LVK_VIDEO_FORMAT_UYVY: return {1, {2 * cols, 0, 0}};
-    case LVK_VIDEO_FORMAT_AYUV: case LVK_VIDEO_FORMAT_RGBA: case LVK_VIDEO_FORMAT_BGRA: case LVK_VIDEO_FORMAT_BGRX: return {1, {4 * cols, 0, 0}};
-    case LVK_VIDEO_FORMAT_BGR3: return {1, {3 * cols, 0, 0}};
-    case LVK_VIDEO_FORMAT_Y800: return {1, {cols, 0, 0}};
-    default: return {0, {0, 0, 0}};
-    }
-}
-bool is_direct4(int vf) { return vf == LVK_VIDEO_FORMAT_RGBA || vf == LVK_VIDEO_FORMAT_BGRA || vf == LVK_VIDEO_FORMAT_BGRX; }
-
-// The output planes of one frame (cols even on 4:2:2: the caller has checked): every plane there, its row inside its pitch, addressable by the sinks; clear
-// of the `n_in` input spans and of one another
-int obs_outputs_ok(lvk_hip_ctx* ctx, const char* name, int vf, void* const o_planes[3], const int o_steps[3], int rows, int cols, const Span* in, int n_in)
-{
-    const ObsRows t = obs_rows(vf, cols);
-    if (t.n == 0) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": video format " + std::to_string(vf) + " is not one FrameIngest::Select knows");
-    Spans out{{}, t.n};
-    for (int i = 0; i < t.n; i++)
-    {
-        LVK_HIP_REQUIRE(ctx, remap_plane_ok(o_planes[i], o_steps[i], rows, t.bytes[i], 1));
-        out.s[i] = span_of(o_planes[i], o_steps[i], rows, t.bytes[i]);
-    }
-    LVK_HIP_REQUIRE(ctx, !is_direct4(vf) || o_steps[0] == 4 * cols);
-    if (!clear_of(in, n_in, out)) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": an output plane overlaps an input (the call is out of place)");
-    if (!disjoint(out)) return ctx->fail(LVK_HIP_ERR_ARG, std::string(name) + ": two output planes overlap");
-    return LVK_HIP_OK;
-}
+// (the OBS video formats that are not 4:2:0 -- lvk_hip_remap_map_obs, lvk_hip_lens_apply_obs: their planes are described in obs_planes.hpp, their
+//  output planes checked by obs_outputs_ok of obs_sinks.hpp)
 
 } // namespace
 

@@ -1,6 +1,6 @@
 // The arithmetic of FSR's robust contrast adaptive sharpening (RCAS; the OpenCL kernel `rcas`, LiveVisionKit/Functions/OpenCL/Sources/FSR.cl:460-535), written
-// once for the kernels of sharpen.hip (packed 8UC3 frames) and scaling_420.hip (the planes of an I420 / NV12 frame): the pixel, its unpacking, the two
-// limiter tables and the rows of a packed frame as a thread of four columns reads them.
+// once for the kernels of sharpen.hip (packed 8UC3 frames), scaling_420.hip (the planes of an I420 / NV12 frame) and scaling_obs.hip (the planes of the
+// other OBS video formats): the pixel, its unpacking, the two limiter tables and the rows of a packed frame as a thread of four columns reads them.
 //
 // Arithmetic contract (must stay in lock-step with the specification the tests check against): binary32 IEEE ops, no implicit contraction, fused
 // multiply-adds exactly where written as fma(), native_recip = v_rcp_f32 as in the reference's compiled kernel (see fill_tables), min/max with fmin/fmax

@@ -12,6 +12,7 @@
 // one outside those of an output row.
 #include "lvk_hip_internal.hpp"
 #include "rcas_core.hpp"
+#include "rcas_src.hpp"
 #include "yuv420_core.hpp"
 
 #include <cmath>
@@ -20,41 +21,6 @@ using namespace rcas;
 using namespace yuv420;
 
 namespace {
-
-constexpr int ROWS = 4;                                   // rows per thread, as lvk_launch_sharpen chose them
-
-// Rows of a packed 8UC3 frame, loaded as k_rcas loads them.  The last thread of a row with cols % 4 == 2 has no 12 bytes of its own: it reads its six
-// pixels one by one, columns clamped into the row.
-struct PackedSrc
-{
-    const uint8_t* src; int step;
-    struct Raw { RawRow r[ROWS + 2]; };
-
-    __device__ __forceinline__ void load(Raw& raw, int x0, int y0, int rows, int cols, int) const
-    {
-        if (x0 + RCAS_PXT <= cols)
-        {
-#pragma unroll
-            for (int r = 0; r < ROWS + 2; r++) raw.r[r] = load_row(src, step, y0 - 1 + r, rows, x0, cols);
-            return;
-        }
-#pragma unroll
-        for (int r = 0; r < ROWS + 2; r++)
-        {
-            const uint8_t* rp = src + (long)min(max(y0 - 1 + r, 0), rows - 1) * step;
-            uint32_t p[RCAS_PXT + 2];
-#pragma unroll
-            for (int j = 0; j < RCAS_PXT + 2; j++) p[j] = load_px_raw(rp + 3 * (long)min(max(x0 - 1 + j, 0), cols - 1));
-            raw.r[r] = RawRow{p[1] | (p[2] << 24), (p[2] >> 8) | (p[3] << 16), (p[3] >> 16) | (p[4] << 8), p[0], p[5]};
-        }
-    }
-    __device__ __forceinline__ Row row(const Raw& raw, int r) const { return unpack_row(raw.r[r]); }
-    __device__ __forceinline__ void centre(const Raw& raw, int r, uint32_t (&c)[RCAS_PXT]) const
-    {
-        const RawRow& m = raw.r[r];
-        c[0] = m.w0 & 0xffffffu; c[1] = (m.w0 >> 24) | ((m.w1 & 0xffffu) << 8); c[2] = (m.w1 >> 16) | ((m.w2 & 0xffu) << 16); c[3] = m.w2 >> 8;
-    }
-};
 
 // The planes of an I420 / NV12 frame: the packed pixel (Y, up(U), up(V)) the ingest would write is formed in registers.  A thread's 6 x 6 pixels, rows
 // y0 - 1 .. y0 + 4 and columns x0 - 1 .. x0 + 4, need the chroma rows k0 - 1 .. k0 + 2 (k0 = y0 / 2) and columns c0 - 1 .. c0 + 2 (c0 = x0 / 2): one
@@ -217,27 +183,23 @@ int launch_rcas_420(lvk_hip_ctx* ctx, const Src& src, const PlanesOut& out, int 
 
 } // namespace
 
-extern "C" int lvk_hip_scale_yuv420(lvk_hip_ctx* ctx,
-                                    const void* d_y, int y_step, const void* d_u, int u_step, const void* d_v, int v_step, int src_rows, int src_cols,
-                                    void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int dst_rows, int dst_cols,
-                                    int nv12, float sharpness)
+// lvk_hip_scale_yuv420 behind its entry guard: also the I420 / I40A / NV12 route of lvk_hip_scale_obs (scaling_obs.hip)
+int lvk_scale_420(lvk_hip_ctx* ctx, const char* name, const yuv420::PlaneSet& src, const yuv420::PlaneSet& dst, float sharpness)
 {
-    LVK_HIP_ENTRY(ctx);
-    const PlaneSet src = plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, src_rows, src_cols);
-    const PlaneSet dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, dst_rows, dst_cols);
+    const int nv12 = dst.nv12, src_rows = src.rows, src_cols = src.cols, dst_rows = dst.rows, dst_cols = dst.cols;
     LVK_HIP_REQUIRE(ctx, well_formed(src) && well_formed(dst));
     LVK_HIP_REQUIRE(ctx, dst_cols >= src_cols && dst_rows >= src_rows);                      // Image.cpp:157
     LVK_HIP_REQUIRE(ctx, sharpness >= 0.0f && sharpness <= 1.0f);                            // LVK_ASSERT_01, Image.cpp:210 (a NaN fails both)
     int rc;
     // out of place: the sharpening and the chroma up-sampling read their neighbours
     const Spans src_spans = spans_of(src);
-    if ((rc = require_out_of_place(ctx, "lvk_hip_scale_yuv420", src_spans.s, src_spans.n, dst)) != LVK_HIP_OK) return rc;
+    if ((rc = require_out_of_place(ctx, name, src_spans.s, src_spans.n, dst)) != LVK_HIP_OK) return rc;
     const float sharp = exp2f(-2.0f * (1.0f - sharpness));                                   // Image.cpp:227
+    const Planes in = src.in();
     const PlanesOut out = dst.out();
 
     if (dst_rows == src_rows && dst_cols == src_cols)       // lvk::upscale copies (Image.cpp:162-166): the sharpening reads the planes itself
     {
-        const Planes in = src.in();
         const int flags = access_flags(&src, dst);
         return nv12 ? launch_rcas_420<PlanarSrc<true>, true>(ctx, PlanarSrc<true>{in}, out, dst_rows, dst_cols, sharp, flags)
                     : launch_rcas_420<PlanarSrc<false>, false>(ctx, PlanarSrc<false>{in}, out, dst_rows, dst_cols, sharp, flags);
@@ -250,7 +212,7 @@ extern "C" int lvk_hip_scale_yuv420(lvk_hip_ctx* ctx,
     void *d_small = nullptr, *d_big = nullptr;
     if ((rc = lvk_hip_malloc(ctx, (size_t)s_step * src_rows, &d_small)) != LVK_HIP_OK) return rc;
     if ((rc = lvk_hip_malloc(ctx, (size_t)p_step * dst_rows, &d_big)) == LVK_HIP_OK
-        && (rc = lvk_launch_ingest_yuv420(ctx, ctx->stream, d_y, y_step, d_u, u_step, d_v, v_step, nv12, src_rows, src_cols, d_small, s_step)) == LVK_HIP_OK
+        && (rc = lvk_launch_ingest_yuv420(ctx, ctx->stream, in.y, in.ys, in.u, in.us, in.v, in.vs, nv12, src_rows, src_cols, d_small, s_step)) == LVK_HIP_OK
         && (rc = lvk_launch_upscale(ctx, ctx->stream, d_small, s_step, src_rows, src_cols, d_big, p_step, dst_rows, dst_cols, 1)) == LVK_HIP_OK)
     {
         const PackedSrc big{(const uint8_t*)d_big, p_step};
@@ -260,4 +222,14 @@ extern "C" int lvk_hip_scale_yuv420(lvk_hip_ctx* ctx,
     (void)lvk_hip_free(ctx, d_small);
     (void)lvk_hip_free(ctx, d_big);
     return rc;
+}
+
+extern "C" int lvk_hip_scale_yuv420(lvk_hip_ctx* ctx,
+                                    const void* d_y, int y_step, const void* d_u, int u_step, const void* d_v, int v_step, int src_rows, int src_cols,
+                                    void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step, int dst_rows, int dst_cols,
+                                    int nv12, float sharpness)
+{
+    LVK_HIP_ENTRY(ctx);
+    return lvk_scale_420(ctx, "lvk_hip_scale_yuv420", plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, src_rows, src_cols),
+                         plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, dst_rows, dst_cols), sharpness);
 }
