@@ -4,7 +4,8 @@
 // frames FrameIngest::upload_obs_frame makes.  filter() dispatches on the frame's type: 8UC3 (BGR / RGB / YUV), 8UC1 of format GRAY and 8UC4 of format
 // BGRA / RGBA (lvk_hip_deblock_apply_gray / _c4: the reference's calls per channel, alpha included); draw_influence is 8UC3 only, like the reference's,
 // whose overlay is an 8UC3 buffer (DeblockingFilter.cpp:120).  apply(VideoFrame420, VideoFrame420) takes the plugin's I420 / NV12 planes in one call
-// (lvk_hip_deblock_apply_yuv420, out of place).  Included by LiveVisionKit.hpp.
+// (lvk_hip_deblock_apply_yuv420, out of place), apply(VideoFrameOBS, VideoFrameOBS) the planes of every OBS video format
+// (lvk_hip_deblock_apply_obs).  Included by LiveVisionKit.hpp.
 #pragma once
 
 #include "LiveVisionKit.hpp"
@@ -72,6 +73,33 @@ public:
                                                       output.y(), output.y_step(), output.u(), output.uv_step(), output.v(), output.uv_step(),
                                                       input.nv12 ? 1 : 0, input.rows, input.cols, nullptr),
                          "DeblockingFilter::apply(4:2:0)");
+        });
+        sync_gpu(profile); frame_timer().stop();
+    }
+
+    // A frame of ANY OBS video format in one call (lvk_hip_deblock_apply_obs), byte for byte FrameIngest::to_ocl -> apply(frame, frame) ->
+    // FrameIngest::to_obs without the packed frame between them.  Out of place: `output` is created at the input's size, format and context (bytes
+    // to_obs leaves alone -- the last quarter of an RGBA / BGRA / BGRX plane -- are whatever the fresh block held); the input planes are not written;
+    // filter_region() and draw_influence (on a packed 8UC3 frame) answer as after the packed apply on the ingested frame.
+    void apply(const VideoFrameOBS& input, VideoFrameOBS& output, const bool profile = false)
+    {
+        LVK_HIP_ASSERT(!input.empty());
+        LVK_HIP_ASSERT(&input != &output);
+        if (!m_Handle)
+        {
+            m_Ctx = input.context();
+            const lvk_deblock_settings s = to_c(m_Settings);
+            hip::ContextLock lock(m_Ctx->mutex());
+            m_Ctx->check(lvk_hip_deblock_create(m_Ctx->get(), &s, &m_Handle), "DeblockingFilter");
+        }
+        sync_gpu(profile); frame_timer().start();
+        output.create({input.cols, input.rows}, input.format, input.context());
+        LVK_HIP_ASSERT(output.data[0] != input.data[0]);
+        output.timestamp = input.timestamp;
+        run(input.context(), [&] {
+            m_Ctx->check(lvk_hip_deblock_apply_obs(m_Handle, input.format, reinterpret_cast<const void* const*>(input.data), input.linesize,
+                                                   reinterpret_cast<void* const*>(output.data), output.linesize, input.rows, input.cols, nullptr),
+                         "DeblockingFilter::apply(OBS)");
         });
         sync_gpu(profile); frame_timer().stop();
     }

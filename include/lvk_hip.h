@@ -832,7 +832,8 @@ int lvk_hip_track_chain(lvk_hip_ctx* ctx, const lvk_track_chain_desc* desc, lvk_
 int lvk_hip_deblock_get_grid(lvk_hip_deblock* deb, uint8_t* mean, uint8_t* grid, float* keep_block, int capacity, int extent_xy[2]);
 
 /* The deblocking filter on the planes of an I420 / NV12 frame in one call, lvk_hip_deblock_apply_yuv420 on the same handle, is declared in
- * lvk_hip_deblock_420.h, which this header includes at its end like lvk_hip_deblock_px.h. */
+ * lvk_hip_deblock_420.h, which this header includes at its end like lvk_hip_deblock_px.h; the same on the planes of every OBS video format,
+ * lvk_hip_deblock_apply_obs, in lvk_hip_deblock_obs.h, which that header includes. */
 
 /* CAS host constant (CasSetup's const1.x, float32, each operation rounded on its own): peak = -(1 / (5 s + ((-8) s + 8))) with
  * s = clamp(sharpness, 0, 1).  Needs no device.  LVK_HIP_ERR_ARG for a NaN sharpness or a NULL peak. */
@@ -940,6 +941,6 @@ int  lvk_hip_lens_apply_obs(lvk_hip_lens* lens, int video_format, const void* co
 #endif
 
 #include "lvk_hip_scaling_420.h"  /* lvk_hip_scale_yuv420 (PART 2); it includes lvk_hip_scaling_obs.h */
-#include "lvk_hip_deblock_420.h"  /* lvk_hip_deblock_apply_yuv420 (PART 2) */
+#include "lvk_hip_deblock_420.h"  /* lvk_hip_deblock_apply_yuv420 (PART 2); it includes lvk_hip_deblock_obs.h */
 #include "lvk_hip_deblock_px.h"   /* lvk_hip_deblock_apply_gray / _c4 (PART 2) */
 #endif /* LVK_HIP_H */

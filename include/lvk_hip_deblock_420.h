@@ -30,4 +30,6 @@ int lvk_hip_deblock_apply_yuv420(lvk_hip_deblock* deb, const void* d_y, int y_st
 }
 #endif
 
+#include "lvk_hip_deblock_obs.h"  /* lvk_hip_deblock_apply_obs: the same filter on every OBS video format (PART 2) */
+
 #endif /* LVK_HIP_DEBLOCK_420_H */

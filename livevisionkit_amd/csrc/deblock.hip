@@ -40,13 +40,6 @@ namespace {
 constexpr int kMedTile = 16;              // median: 16 x 16 outputs per block
 constexpr int kMedLdsMaxK = 113;          // (16 + k - 1)^2 packed pixels fit 64 KiB of LDS up to this k; larger k read global memory
 
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // The grey of the block statistics.  GRAY: the byte itself.  Else RGB2Gray<uchar> of the colour bytes; blue_shift: the bit position of the blue
 // byte (0: BGR / BGRA, 16: RGB / RGBA), alpha ignored; negative (three-channel YUV): byte 0.  blue_shift is a kernel argument, uniform over the grid.
 template <int BPP>
@@ -90,19 +83,8 @@ void k_deblock_stats(const uint8_t* __restrict__ frame, int step, int blue_shift
     const int bx = blockIdx.x * 4 + (threadIdx.x >> 6), by = blockIdx.y;
     if (bx >= ex) return;                       // whole waves only
     const uint8_t* base = frame + (size_t)by * bs * step + (size_t)bx * bs * BPP;
-    long long sum = 0;
-    block_visit<BPP>(base, step, bs, blue_shift, dwords, lane, [&](int g) { sum += g; });
-    const int mean = box_mean(wave_sum(sum), bs, inv_area);
-    long long dev = 0;                          // the block's bytes are still in L1 / L2: one HBM read for both passes
-    block_visit<BPP>(base, step, bs, blue_shift, dwords, lane, [&](int g) { dev += abs(g - mean); });
-    const int grid = box_mean(wave_sum(dev), bs, inv_area);
-    if (lane == 0)
-    {
-        const size_t o = (size_t)by * ex + bx;
-        mean_out[o] = (uint8_t)mean;
-        grid_out[o] = (uint8_t)grid;
-        keep_out[o] = (float)((double)min(grid, levels) * level_step);
-    }
+    block_stats([&](auto f) { block_visit<BPP>(base, step, bs, blue_shift, dwords, lane, f); }, bs, inv_area, levels, level_step, lane,
+                (size_t)by * ex + bx, mean_out, grid_out, keep_out);
 }
 
 // INTER_AREA of the region (BPP channels) to hs x ws, one thread per output pixel: down_pixel of deblock_core.hpp on the packed frame's pixels

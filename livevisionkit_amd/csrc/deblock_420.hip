@@ -46,10 +46,6 @@ __device__ __forceinline__ uint32_t pixel_420(const Row420& r, int cc, int x)
     return (uint32_t)r.y[x] | ((uint32_t)u << 8) | ((uint32_t)v << 16);
 }
 
-// A pixel of the median frame (three bytes, any alignment) as ONE load: the dword at its address, whose fourth byte is the next pixel's first or,
-// behind the last pixel, the slack deblock::reserve leaves behind the frame; byte_of never looks at it.
-__device__ __forceinline__ uint32_t load_tap(const uint8_t* __restrict__ p) { return reinterpret_cast<const P4*>(p)->w; }
-
 // the horizontal sums of the four luma columns 2 c0 .. 2 c0 + 3 from the samples c0 - 1 .. c0 + 2
 __device__ __forceinline__ void up_h4(uint32_t w, int (&t)[4])
 {
@@ -223,15 +219,12 @@ void k_deblock_blend_420(Planes in, PlanesOut out, int rows, int cols, int rh, i
 
 } // namespace
 
-extern "C" int lvk_hip_deblock_apply_yuv420(lvk_hip_deblock* d, const void* d_y, int y_step, const void* d_u, int u_step, const void* d_v, int v_step,
-                                            void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step,
-                                            int nv12, int rows, int cols, int region_xywh[4])
+// lvk_hip_deblock_apply_yuv420 behind its entry guard: also the I420 / I40A / NV12 route of lvk_hip_deblock_apply_obs (deblock_obs.hip)
+int deblock::apply_420(lvk_hip_deblock* d, const char* who, const PlaneSet& src, const PlaneSet& dst, int region_xywh[4])
 {
-    if (!d) return LVK_HIP_ERR_ARG;
     lvk_hip_ctx* ctx = d->ctx;
-    LVK_HIP_ENTRY(ctx);
-    const std::string name("lvk_hip_deblock_apply_yuv420");
-    const PlaneSet src = plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols), dst = plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols);
+    const std::string name(who);
+    const int nv12 = dst.nv12, rows = dst.rows, cols = dst.cols;
     LVK_HIP_REQUIRE(ctx, well_formed(src) && well_formed(dst));
     int rc;
     // out of place: the chroma up-sampling reads its neighbours
@@ -245,11 +238,11 @@ extern "C" int lvk_hip_deblock_apply_yuv420(lvk_hip_deblock* d, const void* d_y,
     const Planes in = src.in();
     const PlanesOut out = dst.out();
     const int crows = rows / 2;
-    if ((rc = launch_stats_plane(d, in.y, y_step, g)) != LVK_HIP_OK) return rc;
+    if ((rc = launch_stats_plane(d, in.y, in.ys, g)) != LVK_HIP_OK) return rc;
     {
         const float inv_area_s = g.fast ? 1.0f / (float)((long long)g.iscale * g.iscale) : 0.0f;
         const dim3 grid((g.ws + 63) / 64, (g.hs + 3) / 4), block(64, 4);
-        const int y_dw = aligned_to(d_y, y_step, 4) ? 1 : 0;
+        const int y_dw = aligned_to(in.y, in.ys, 4) ? 1 : 0;
         if (nv12)
             hipLaunchKernelGGL(k_deblock_down_420<true>, grid, block, 0, ctx->stream, in, rows, cols, g.rh, g.rw, d->d_small, g.hs, g.ws, g.fast ? g.iscale : 0,
                                inv_area_s, (const int2*)d->d_xr, (const AreaTabEntry*)d->d_xt, (const int2*)d->d_yr, (const AreaTabEntry*)d->d_yt, y_dw);
@@ -277,4 +270,14 @@ extern "C" int lvk_hip_deblock_apply_yuv420(lvk_hip_deblock* d, const void* d_y,
     }
     if (region_xywh) { region_xywh[0] = 0; region_xywh[1] = 0; region_xywh[2] = g.rw; region_xywh[3] = g.rh; }
     return LVK_HIP_OK;
+}
+
+extern "C" int lvk_hip_deblock_apply_yuv420(lvk_hip_deblock* d, const void* d_y, int y_step, const void* d_u, int u_step, const void* d_v, int v_step,
+                                            void* o_y, int oy_step, void* o_u, int ou_step, void* o_v, int ov_step,
+                                            int nv12, int rows, int cols, int region_xywh[4])
+{
+    if (!d) return LVK_HIP_ERR_ARG;
+    LVK_HIP_ENTRY(d->ctx);
+    return apply_420(d, "lvk_hip_deblock_apply_yuv420", plane_set(d_y, y_step, d_u, u_step, d_v, v_step, nv12, rows, cols),
+                     plane_set(o_y, oy_step, o_u, ou_step, o_v, ov_step, nv12, rows, cols), region_xywh);
 }

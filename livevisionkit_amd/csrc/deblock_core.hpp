@@ -1,10 +1,12 @@
-// What the deblocking filter's two units share: deblock.hip (packed frames of one, three and four bytes per pixel) and deblock_420.hip (I420 / NV12
-// planes in and out).  The handle, the per-pixel arithmetic of the specification (tests/np_deblock.py),
-// the body of the 1 / filter_scaling downscale with the pixel fetch as a parameter, the geometry of one apply with its refusals, the buffers and the
-// area tables.  Every product and sum is its own rounding (-ffp-contract=off).
+// What the deblocking filter's three units share: deblock.hip (packed frames of one, three and four bytes per pixel), deblock_420.hip (I420 / NV12
+// planes in and out) and deblock_obs.hip (the planes of the other OBS video formats, section 31).  The handle, the per-pixel
+// arithmetic of the specification (tests/np_deblock.py), the two passes of the block statistics with the walk over a block's
+// pixels as a parameter, the body of the 1 / filter_scaling downscale with the pixel fetch as a parameter, the geometry of one apply with its
+// refusals, the buffers and the area tables.  Every product and sum is its own rounding (-ffp-contract=off).
 #pragma once
 
 #include "lvk_hip_internal.hpp"
+#include "yuv420_core.hpp"
 
 #include <cmath>
 #include <algorithm>
@@ -53,6 +55,10 @@ struct Geometry
 int launch_stats_plane(lvk_hip_deblock* d, const uint8_t* plane, int step, const Geometry& g);
 int launch_median_c3(lvk_hip_deblock* d, const Geometry& g);
 
+// lvk_hip_deblock_apply_yuv420 behind its entry guard (deblock_420.hip): also the I420 / I40A / NV12 route of lvk_hip_deblock_apply_obs
+// (deblock_obs.hip); `name` is the entry's
+int apply_420(lvk_hip_deblock* d, const char* name, const yuv420::PlaneSet& src, const yuv420::PlaneSet& dst, int region_xywh[4]);
+
 __device__ __forceinline__ int sat_u8(float v)           // saturate_cast<uchar>(float): round half to even, clamp
 {
     const float r = rintf(v);
@@ -66,6 +72,35 @@ __device__ __forceinline__ int box_mean(long long sum, int bs, float inv_area)
 }
 
 __device__ __forceinline__ int byte_of(uint32_t v, int c) { return (int)((v >> (8 * c)) & 255u); }
+
+__device__ __forceinline__ long long wave_sum(long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The statistics of one macroblock by one wave, two passes: the exact integer block mean of the grey, then the mean absolute deviation from it, and
+// keep_block = float(min(grid, L) * (1.0 / L)).  visit(f) calls f(grey) for every pixel of the block, the wave's lanes striding over it: the bytes
+// of a packed frame (k_deblock_stats, deblock.hip) or the luma bytes of a packed YUV layout (k_deblock_stats_luma, deblock_obs.hip).  The second
+// pass reads the same, cache-resident bytes.  o: the block's index in the three grids.
+template <typename Visit>
+__device__ __forceinline__ void block_stats(Visit visit, int bs, float inv_area, int levels, double level_step, int lane, size_t o,
+                                            uint8_t* __restrict__ mean_out, uint8_t* __restrict__ grid_out, float* __restrict__ keep_out)
+{
+    long long sum = 0;
+    visit([&](int g) { sum += g; });
+    const int mean = box_mean(wave_sum(sum), bs, inv_area);
+    long long dev = 0;                          // the block's bytes are still in L1 / L2: one HBM read for both passes
+    visit([&](int g) { dev += abs(g - mean); });
+    const int grid = box_mean(wave_sum(dev), bs, inv_area);
+    if (lane == 0)
+    {
+        mean_out[o] = (uint8_t)mean;
+        grid_out[o] = (uint8_t)grid;
+        keep_out[o] = (float)((double)min(grid, levels) * level_step);
+    }
+}
 
 template <int BPP>
 __device__ __forceinline__ uint32_t load_pixel(const uint8_t* __restrict__ p)       // a pixel's channels in bytes 0 .. BPP - 1
@@ -138,6 +173,10 @@ __device__ __forceinline__ void down_pixel(Row row, Px px, uint8_t* __restrict__
     for (int c = 0; c < BPP; c++) out |= (uint32_t)sat_u8(a[c]) << (8 * c);
     store_pixel<BPP>(d, out);
 }
+
+// A pixel of the median frame (three bytes, any alignment) as ONE load: the dword at its address, whose fourth byte is the next pixel's first or,
+// behind the last pixel, the slack deblock::reserve leaves behind the frame; byte_of never looks at it.
+__device__ __forceinline__ uint32_t load_tap(const uint8_t* __restrict__ p) { return reinterpret_cast<const yuv420::P4*>(p)->w; }
 
 // `keep` of one pixel: the float bilinear of keep_block (k0 / k1: its two rows)
 __device__ __forceinline__ float keep_at(const float* __restrict__ k0, const float* __restrict__ k1, const LinTabEntry& tx, const LinTabEntry& ty)

@@ -1,7 +1,7 @@
 // The planes of the OBS video formats as the entries that take "every format FrameIngest::Select accepts" describe them (lvk_hip_lens_apply_obs,
-// lvk_hip_remap_map_obs, lvk_hip_scale_obs): which formats are 4:2:0, the planes of the others and the bytes of their rows, the parity of a frame size, the
-// byte spans of a frame's planes, and the route lvk_hip_scale_obs takes.  Plain C++ on top of planes420.hpp, no HIP: tests/cpp/obs_planes_check.cpp
-// compiles it on the CPU.
+// lvk_hip_remap_map_obs, lvk_hip_scale_obs, lvk_hip_deblock_apply_obs): which formats are 4:2:0, the planes of the others and the bytes of their rows, the
+// parity of a frame size, the byte spans of a frame's planes, and the routes lvk_hip_scale_obs and lvk_hip_deblock_apply_obs take.  Plain C++ on top of
+// planes420.hpp, no HIP: tests/cpp/obs_planes_check.cpp and tests/cpp/deblock_route_check.cpp compile it on the CPU.
 #pragma once
 
 #include "planes420.hpp"
@@ -75,6 +75,37 @@ inline ScaleRoute scale_route(int vf, bool equal_sizes)
     if (vf == LVK_VIDEO_FORMAT_BGR3 || is_direct4(vf)) return ScaleRoute::Bgr;
     if (obs_rows(vf, 2).n == 0) return ScaleRoute::None;
     return equal_sizes ? ScaleRoute::FusedPlanes : ScaleRoute::FusedPacked;
+}
+
+// lvk_hip_deblock_apply_obs: the launches behind one call, by format
+enum class DeblockRoute
+{
+    None,           // not a format FrameIngest::Select knows
+    Planes420,      // the body of lvk_hip_deblock_apply_yuv420
+    Fused,          // statistics on the luma, downscale from the planes, median, blend into the planes: no packed frame (4:2:2, 4:4:4, AYUV)
+    Bgr,            // a copy, then the packed three-channel apply in place on the output: BGR3 at its pitch, RGBA / BGRA / BGRX on the 3 * cols view
+    Gray            // a copy, then the gray apply in place on the output plane
+};
+
+inline DeblockRoute deblock_route(int vf)
+{
+    if (is_420(vf)) return DeblockRoute::Planes420;
+    if (vf == LVK_VIDEO_FORMAT_Y800) return DeblockRoute::Gray;
+    if (vf == LVK_VIDEO_FORMAT_BGR3 || is_direct4(vf)) return DeblockRoute::Bgr;
+    return obs_rows(vf, 2).n == 0 ? DeblockRoute::None : DeblockRoute::Fused;
+}
+
+// Where the luma bytes of a row of a fused format lie: the first at byte `first`, the next `stride` bytes on.  Planar Y planes: {0, 1}.
+struct LumaBytes { int first, stride; };
+inline LumaBytes luma_bytes(int vf)
+{
+    switch (vf)
+    {
+    case LVK_VIDEO_FORMAT_YUY2: case LVK_VIDEO_FORMAT_YVYU: return {0, 2};
+    case LVK_VIDEO_FORMAT_UYVY: return {1, 2};
+    case LVK_VIDEO_FORMAT_AYUV: return {1, 4};
+    default: return {0, 1};
+    }
 }
 
 } // namespace obs

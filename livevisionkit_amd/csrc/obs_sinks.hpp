@@ -1,4 +1,4 @@
-// What the units that write the planes of an OBS video format outside 4:2:0 from a kernel share (remap_obs.hip, scaling_obs.hip, and lens_filter.hip for
+// What the units that write the planes of an OBS video format outside 4:2:0 from a kernel share (remap_obs.hip, scaling_obs.hip, deblock_obs.hip, and lens_filter.hip for
 // the checks): the per-format plane sinks -- planar or packed 4:2:2, planar 4:4:4, AYUV -- as FrameIngest::to_obs would write the frame (reference:
 // Modules/OBS-Plugin/Interop/FrameIngest.cpp:526-557 I4XXIngest, :640-666 P422Ingest, :690-703 P444Ingest), the one format -> sink switch (with_obs_sink) and
 // the one check of a frame's output planes (obs_outputs_ok).  A sink takes a thread's four horizontally adjacent packed pixels:
@@ -87,6 +87,28 @@ struct Sink444
         }
     }
 };
+
+// A thread's finished row of four pixels goes to the sink (scaling_obs.hip, deblock_obs.hip).  AYUV alone has a wider form here: four whole pixels whose 16
+// bytes lie on a 16-byte boundary leave as ONE store, as k_egress_444_dw writes them (ingest.hip) -- the sink's four dword stores, 16 bytes apart across the
+// wave, cost the 4K frame 20 us.  Everything else, and every other row of an AYUV plane, is the sink's own store.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <class Sink>
+__device__ __forceinline__ void store_row(const Sink& sink, int x0, int y, int npx, const uint32_t (&px)[PXT])
+{
+    sink.store(x0, y, npx, px, true, 0);
+}
+
+__device__ __forceinline__ void store_row(const Sink444<1>& sink, int x0, int y, int npx, const uint32_t (&px)[PXT])
+{
+    uint8_t* d = sink.p0 + (__umul24((uint32_t)y, (uint32_t)sink.s0) + 4u * (uint32_t)x0);
+    if (npx == PXT && (reinterpret_cast<uintptr_t>(d) & 15u) == 0)
+    {
+        const u32x4 w = {255u | (px[0] << 8), 255u | (px[1] << 8), 255u | (px[2] << 8), 255u | (px[3] << 8)};
+        __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(d));
+    }
+    else sink.store(x0, y, npx, px, true, 0);
+}
 
 // The sink of `video_format` over the caller's planes, checked, handed to launch(sink): the one switch of the two launchers below.  Plane i holds
 // rows x `c` samples of `bpp` bytes; 4:2:2 has an even width.

@@ -129,28 +129,8 @@ struct PlaneSrc
     }
 };
 
-// A thread's finished row of four pixels goes to the sink.  AYUV alone has a wider form here: four whole pixels whose 16 bytes lie on a 16-byte boundary leave
-// as ONE store, as k_egress_444_dw writes them (ingest.hip) -- the sink's four dword stores, 16 bytes apart across the wave, cost the 4K frame 20 us
-// (DESIGN.md section 30).  Everything else, and every other row of an AYUV plane, is the sink's own store.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <class Sink>
-__device__ __forceinline__ void store_row(const Sink& sink, int x0, int y, int npx, const uint32_t (&px)[NPX])
-{
-    sink.store(x0, y, npx, px, true, 0);
-}
-
-__device__ __forceinline__ void store_row(const Sink444<1>& sink, int x0, int y, int npx, const uint32_t (&px)[NPX])
-{
-    uint8_t* d = sink.p0 + (__umul24((uint32_t)y, (uint32_t)sink.s0) + 4u * (uint32_t)x0);
-    if (npx == NPX && (reinterpret_cast<uintptr_t>(d) & 15u) == 0)
-    {
-        const u32x4 w = {255u | (px[0] << 8), 255u | (px[1] << 8), 255u | (px[2] << 8), 255u | (px[3] << 8)};
-        __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(d));
-    }
-    else sink.store(x0, y, npx, px, true, 0);
-}
-
+// (a thread's finished row of four pixels goes to the sink through store_row of obs_sinks.hpp)
+//
 // lvk_hip_sharpen of the frame `src` describes, then lvk_hip_egress_obs of the result through `sink`, without that result: one thread per 4 x ROWS pixels.
 template <class Src, class Sink>
 __global__ __launch_bounds__(256)

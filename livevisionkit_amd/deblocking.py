@@ -2,7 +2,7 @@
 Same method names: configure / apply / draw_influence / filter_region.  Frames are torch uint8 tensors [rows, cols, 3] on the GPU
 (any row pitch: a view with stride(1) == 3 and stride(2) == 1), filtered IN PLACE like the reference's apply(frame, frame).  apply also takes
 GRAY frames [rows, cols] and BGRA / RGBA frames [rows, cols, 4] (lvk_hip_deblock_apply_gray / _c4).  apply_yuv420 takes the planes of an I420 / NV12
-frame and writes new planes (lvk_hip_deblock_apply_yuv420)."""
+frame and writes new planes (lvk_hip_deblock_apply_yuv420), apply_obs the planes of any OBS video format (lvk_hip_deblock_apply_obs)."""
 import ctypes
 
 import numpy as np
@@ -81,6 +81,23 @@ class DeblockingFilter:
 
         region = (_c.c_int * 4)()
         self.ctx._check(self.lib.lvk_hip_deblock_apply_yuv420(self.handle, *_planes420_args(planes, nv12), *_planes420_args(out, nv12), 1 if nv12 else 0, rows, cols, region))
+        return out, tuple(region)
+
+    def apply_obs(self, fmt, planes, out=None):
+        """Deblocks the planes of one frame of ANY OBS video format OUT OF PLACE in one call (lvk_hip_deblock_apply_obs): byte for byte the
+        ctx.ingest_obs -> apply(the format's frame format) -> ctx.egress_obs chain.  `fmt` = a name of Context.VIDEO_FORMATS or its number; `planes`
+        as ctx.ingest_obs takes them; `out` = the planes of the output frame (allocated from the input planes' shapes when None -- bytes the egress
+        leaves alone are then undefined; rows may be padded).  Returns (planes, region); asynchronous on the context's stream."""
+        import torch
+        planes = list(planes)
+        rows, cols = int(planes[0].shape[0]), int(planes[0].shape[1])
+        out = [torch.empty(tuple(p.shape), dtype=torch.uint8, device=p.device) for p in planes] if out is None else list(out)
+        if len(out) != len(planes):
+            raise ValueError("`out` holds one plane per input plane")
+        iptr, istep = self.ctx._obs_args(planes)
+        optr, ostep = self.ctx._obs_args(out)
+        region = (_c.c_int * 4)()
+        self.ctx._check(self.lib.lvk_hip_deblock_apply_obs(self.handle, self.ctx.video_format(fmt), iptr, istep, optr, ostep, rows, cols, region))
         return out, tuple(region)
 
     def draw_influence(self, frame, fmt=FORMAT_YUV):
