@@ -42,4 +42,6 @@ int lvk_hip_deblock_apply_obs(lvk_hip_deblock* deb, int video_format,
 }
 #endif
 
+#include "lvk_hip_cas_obs.h"  /* lvk_hip_cas_yuv420 / lvk_hip_cas_obs: the filter that follows this one in a chain, on the same planes (PART 2) */
+
 #endif /* LVK_HIP_DEBLOCK_OBS_H */

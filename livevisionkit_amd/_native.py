@@ -214,6 +214,13 @@ _SIG_DEBLOCK_OBS = {
     "lvk_hip_deblock_apply_obs": (_c.c_int, [_P, _c.c_int, _P * 3, _c.c_int * 3, _P * 3, _c.c_int * 3, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
 }
 
+# what include/lvk_hip_cas_obs.h declares (lvk_hip.h includes it through lvk_hip_deblock_420.h and lvk_hip_deblock_obs.h; its pin: tests/test_cas_obs_spec.py)
+_SIG_CAS_OBS = {
+    "lvk_hip_cas_yuv420": (_c.c_int, [_P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                      _c.c_float]),
+    "lvk_hip_cas_obs": (_c.c_int, [_P, _c.c_int, _P * 3, _c.c_int * 3, _P * 3, _c.c_int * 3, _c.c_int, _c.c_int, _c.c_float]),
+}
+
 _lib = None
 
 
@@ -247,6 +254,11 @@ def symbols_deblock_obs():
     return sorted(_SIG_DEBLOCK_OBS.keys())
 
 
+def symbols_cas_obs():
+    """The names include/lvk_hip_cas_obs.h declares."""
+    return sorted(_SIG_CAS_OBS.keys())
+
+
 def load():
     """Load liblvk_hip.so and bind every declared symbol; raises if the library or a symbol is missing."""
     global _lib
@@ -258,7 +270,8 @@ def load():
             "(or `make -C livevisionkit_amd/csrc`). There is no CPU fallback.")
     import torch  # noqa: F401  (loads the process-wide HIP runtime first)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX, **_SIG_DEBLOCK_420, **_SIG_SCALING_420, **_SIG_SCALING_OBS, **_SIG_DEBLOCK_OBS}.items():
+    for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX, **_SIG_DEBLOCK_420, **_SIG_SCALING_420, **_SIG_SCALING_OBS, **_SIG_DEBLOCK_OBS,
+                              **_SIG_CAS_OBS}.items():
         fn = getattr(lib, name)      # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

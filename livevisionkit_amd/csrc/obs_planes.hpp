@@ -1,7 +1,8 @@
 // The planes of the OBS video formats as the entries that take "every format FrameIngest::Select accepts" describe them (lvk_hip_lens_apply_obs,
-// lvk_hip_remap_map_obs, lvk_hip_scale_obs, lvk_hip_deblock_apply_obs): which formats are 4:2:0, the planes of the others and the bytes of their rows, the
-// parity of a frame size, the byte spans of a frame's planes, and the routes lvk_hip_scale_obs and lvk_hip_deblock_apply_obs take.  Plain C++ on top of
-// planes420.hpp, no HIP: tests/cpp/obs_planes_check.cpp and tests/cpp/deblock_route_check.cpp compile it on the CPU.
+// lvk_hip_remap_map_obs, lvk_hip_scale_obs, lvk_hip_deblock_apply_obs, lvk_hip_cas_obs): which formats are 4:2:0, the planes of the others and the bytes of their rows, the
+// parity of a frame size, the byte spans of a frame's planes, and the routes lvk_hip_scale_obs, lvk_hip_deblock_apply_obs and lvk_hip_cas_obs take.  Plain
+// C++ on top of planes420.hpp, no HIP: tests/cpp/obs_planes_check.cpp, tests/cpp/deblock_route_check.cpp and tests/cpp/cas_route_check.cpp compile it on
+// the CPU.
 #pragma once
 
 #include "planes420.hpp"
@@ -93,6 +94,24 @@ inline DeblockRoute deblock_route(int vf)
     if (vf == LVK_VIDEO_FORMAT_Y800) return DeblockRoute::Gray;
     if (vf == LVK_VIDEO_FORMAT_BGR3 || is_direct4(vf)) return DeblockRoute::Bgr;
     return obs_rows(vf, 2).n == 0 ? DeblockRoute::None : DeblockRoute::Fused;
+}
+
+// lvk_hip_cas_obs: the launch behind one call, by format
+enum class CasRoute
+{
+    None,           // not a format FrameIngest::Select knows
+    Planes420,      // the body of lvk_hip_cas_yuv420: k_cas_420
+    Fused,          // k_cas_obs<Src, Sink>: one launch, planes to planes (4:2:2, 4:4:4, AYUV)
+    Bgr,            // lvk_hip_cas on three-byte pixels, plane to plane: BGR3 at its pitch, RGBA / BGRA / BGRX on the 3 * cols view
+    Gray            // lvk_hip_cas_gray, plane to plane
+};
+
+inline CasRoute cas_route(int vf)
+{
+    if (is_420(vf)) return CasRoute::Planes420;
+    if (vf == LVK_VIDEO_FORMAT_Y800) return CasRoute::Gray;
+    if (vf == LVK_VIDEO_FORMAT_BGR3 || is_direct4(vf)) return CasRoute::Bgr;
+    return obs_rows(vf, 2).n == 0 ? CasRoute::None : CasRoute::Fused;
 }
 
 // Where the luma bytes of a row of a fused format lie: the first at byte `first`, the next `stride` bytes on.  Planar Y planes: {0, 1}.

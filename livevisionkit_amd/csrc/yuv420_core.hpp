@@ -120,3 +120,6 @@ inline int require_out_of_place(lvk_hip_ctx* ctx, const char* name, const Span* 
 
 // lvk::ScalingFilter on 4:2:0 planes (scaling_420.hip): lvk_hip_scale_yuv420 behind its entry guard, shared with lvk_hip_scale_obs; `name` is the entry's
 int lvk_scale_420(lvk_hip_ctx* ctx, const char* name, const yuv420::PlaneSet& src, const yuv420::PlaneSet& dst, float sharpness);
+
+// lvk::CASFilter on 4:2:0 planes (cas_420.hip): lvk_hip_cas_yuv420 behind its entry guard, shared with lvk_hip_cas_obs; `name` is the entry's
+int lvk_cas_420(lvk_hip_ctx* ctx, const char* name, const yuv420::PlaneSet& src, const yuv420::PlaneSet& dst, float sharpness);
