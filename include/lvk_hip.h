@@ -941,6 +941,6 @@ int  lvk_hip_lens_apply_obs(lvk_hip_lens* lens, int video_format, const void* co
 #endif
 
 #include "lvk_hip_scaling_420.h"  /* lvk_hip_scale_yuv420 (PART 2); it includes lvk_hip_scaling_obs.h */
-#include "lvk_hip_deblock_420.h"  /* lvk_hip_deblock_apply_yuv420 (PART 2); it includes lvk_hip_deblock_obs.h and, through it, lvk_hip_cas_obs.h */
+#include "lvk_hip_deblock_420.h"  /* lvk_hip_deblock_apply_yuv420 (PART 2); it includes lvk_hip_deblock_obs.h and, through it, lvk_hip_cas_obs.h and lvk_hip_fsr_obs.h */
 #include "lvk_hip_deblock_px.h"   /* lvk_hip_deblock_apply_gray / _c4 (PART 2) */
 #endif /* LVK_HIP_H */

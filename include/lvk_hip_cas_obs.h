@@ -53,4 +53,6 @@ int lvk_hip_cas_obs(lvk_hip_ctx* ctx, int video_format,
 }
 #endif
 
+#include "lvk_hip_fsr_obs.h"  /* lvk_hip_fsr_yuv420 / lvk_hip_fsr_obs: the scaler that precedes this filter in a chain, on the same planes (PART 2) */
+
 #endif /* LVK_HIP_CAS_OBS_H */

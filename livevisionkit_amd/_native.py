@@ -221,6 +221,15 @@ _SIG_CAS_OBS = {
     "lvk_hip_cas_obs": (_c.c_int, [_P, _c.c_int, _P * 3, _c.c_int * 3, _P * 3, _c.c_int * 3, _c.c_int, _c.c_int, _c.c_float]),
 }
 
+# what include/lvk_hip_fsr_obs.h declares (lvk_hip.h includes it through lvk_hip_deblock_420.h, lvk_hip_deblock_obs.h and lvk_hip_cas_obs.h; its pin:
+# tests/test_fsr_obs_spec.py)
+_SIG_FSR_OBS = {
+    "lvk_hip_fsr_yuv420": (_c.c_int, [_P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int),
+                                      _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "lvk_hip_fsr_obs": (_c.c_int, [_P, _c.c_int, _P * 3, _c.c_int * 3, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _P * 3, _c.c_int * 3, _c.c_int, _c.c_int]),
+    "lvk_hip_fsr_obs_path": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+}
+
 _lib = None
 
 
@@ -259,6 +268,11 @@ def symbols_cas_obs():
     return sorted(_SIG_CAS_OBS.keys())
 
 
+def symbols_fsr_obs():
+    """The names include/lvk_hip_fsr_obs.h declares."""
+    return sorted(_SIG_FSR_OBS.keys())
+
+
 def load():
     """Load liblvk_hip.so and bind every declared symbol; raises if the library or a symbol is missing."""
     global _lib
@@ -271,7 +285,7 @@ def load():
     import torch  # noqa: F401  (loads the process-wide HIP runtime first)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in {**_SIG, **_SIG_DEBLOCK_PX, **_SIG_DEBLOCK_420, **_SIG_SCALING_420, **_SIG_SCALING_OBS, **_SIG_DEBLOCK_OBS,
-                              **_SIG_CAS_OBS}.items():
+                              **_SIG_CAS_OBS, **_SIG_FSR_OBS}.items():
         fn = getattr(lib, name)      # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

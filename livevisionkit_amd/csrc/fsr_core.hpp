@@ -83,6 +83,48 @@ __device__ __forceinline__ float easu_weight(float ox, float oy, float ppx, floa
     return wb * wa;
 }
 
+// The three-channel pixel function, on texels (r, g, b, luma): shared by fsr.hip and the plane kernels of fsr_planes.hpp.
+// FsrEasuTapF for the tap at (ox, oy) from 'f'
+__device__ __forceinline__ void easu_tap(float3& ac, float& aw, float ox, float oy, float ppx, float ppy, const EasuLobe& lobe, float4 c)
+{
+    const float w = easu_weight(ox, oy, ppx, ppy, lobe);
+    ac.x = ac.x + c.x * w;
+    ac.y = ac.y + c.y * w;
+    ac.z = ac.z + c.z * w;
+    aw = aw + w;
+}
+
+// FsrEasuF from the 12 taps t[dy + 1][dx + 1] (dx, dy in -1 .. 2; the four corners are not used) and the fraction (ppx, ppy) of pp
+__device__ __forceinline__ float3 easu(const float4 (&t)[4][4], float ppx, float ppy)
+{
+    const float4 b = t[0][1], c = t[0][2], e = t[1][0], f = t[1][1], g = t[1][2], h = t[1][3];
+    const float4 i = t[2][0], j = t[2][1], k = t[2][2], l = t[2][3], n = t[3][1], o = t[3][2];
+    const EasuLobe lobe = easu_analyse(b.w, c.w, e.w, f.w, g.w, h.w, i.w, j.w, k.w, l.w, n.w, o.w, ppx, ppy);
+    float3 ac = make_float3(0.0f, 0.0f, 0.0f);
+    float aw = 0.0f;
+    easu_tap(ac, aw, 0.0f, -1.0f, ppx, ppy, lobe, b);
+    easu_tap(ac, aw, 1.0f, -1.0f, ppx, ppy, lobe, c);
+    easu_tap(ac, aw, -1.0f, 1.0f, ppx, ppy, lobe, i);
+    easu_tap(ac, aw, 0.0f, 1.0f, ppx, ppy, lobe, j);
+    easu_tap(ac, aw, 0.0f, 0.0f, ppx, ppy, lobe, f);
+    easu_tap(ac, aw, -1.0f, 0.0f, ppx, ppy, lobe, e);
+    easu_tap(ac, aw, 1.0f, 1.0f, ppx, ppy, lobe, k);
+    easu_tap(ac, aw, 2.0f, 1.0f, ppx, ppy, lobe, l);
+    easu_tap(ac, aw, 2.0f, 0.0f, ppx, ppy, lobe, h);
+    easu_tap(ac, aw, 1.0f, 0.0f, ppx, ppy, lobe, g);
+    easu_tap(ac, aw, 1.0f, 2.0f, ppx, ppy, lobe, o);
+    easu_tap(ac, aw, 0.0f, 2.0f, ppx, ppy, lobe, n);
+    const float inv = 1.0f / aw;                       // correctly rounded (ARcpF1 on OpenGL)
+    const float mnr = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.x, g.x), j.x), k.x);
+    const float mng = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.y, g.y), j.y), k.y);
+    const float mnb = __builtin_fminf(__builtin_fminf(__builtin_fminf(f.z, g.z), j.z), k.z);
+    const float mxr = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(f.x, g.x), j.x), k.x);
+    const float mxg = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(f.y, g.y), j.y), k.y);
+    const float mxb = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(f.z, g.z), j.z), k.z);
+    return make_float3(__builtin_fminf(mxr, __builtin_fmaxf(mnr, ac.x * inv)), __builtin_fminf(mxg, __builtin_fmaxf(mng, ac.y * inv)),
+                       __builtin_fminf(mxb, __builtin_fmaxf(mnb, ac.z * inv)));
+}
+
 // the position of output pixel ip in the region (FsrEasuCon's con0: scale and bias), as every kernel and the host compute it
 __host__ __device__ __forceinline__ float pp_of(int ip, float scale, float bias) { return (float)ip * scale + bias; }
 

@@ -1,8 +1,8 @@
 // The planes of the OBS video formats as the entries that take "every format FrameIngest::Select accepts" describe them (lvk_hip_lens_apply_obs,
-// lvk_hip_remap_map_obs, lvk_hip_scale_obs, lvk_hip_deblock_apply_obs, lvk_hip_cas_obs): which formats are 4:2:0, the planes of the others and the bytes of their rows, the
-// parity of a frame size, the byte spans of a frame's planes, and the routes lvk_hip_scale_obs, lvk_hip_deblock_apply_obs and lvk_hip_cas_obs take.  Plain
-// C++ on top of planes420.hpp, no HIP: tests/cpp/obs_planes_check.cpp, tests/cpp/deblock_route_check.cpp and tests/cpp/cas_route_check.cpp compile it on
-// the CPU.
+// lvk_hip_remap_map_obs, lvk_hip_scale_obs, lvk_hip_deblock_apply_obs, lvk_hip_cas_obs, lvk_hip_fsr_obs): which formats are 4:2:0, the planes of the others and the bytes of their rows, the
+// parity of a frame size, the byte spans of a frame's planes, and the routes lvk_hip_scale_obs, lvk_hip_deblock_apply_obs, lvk_hip_cas_obs and lvk_hip_fsr_obs
+// take.  Plain C++ on top of planes420.hpp, no HIP: tests/cpp/obs_planes_check.cpp, tests/cpp/deblock_route_check.cpp, tests/cpp/cas_route_check.cpp and
+// tests/cpp/fsr_route_check.cpp compile it on the CPU.
 #pragma once
 
 #include "planes420.hpp"
@@ -112,6 +112,27 @@ inline CasRoute cas_route(int vf)
     if (vf == LVK_VIDEO_FORMAT_Y800) return CasRoute::Gray;
     if (vf == LVK_VIDEO_FORMAT_BGR3 || is_direct4(vf)) return CasRoute::Bgr;
     return obs_rows(vf, 2).n == 0 ? CasRoute::None : CasRoute::Fused;
+}
+
+// lvk_hip_fsr_obs: the launches behind one call, by format and by whether the tile's source footprint fits the LDS stage (lvk_hip_fsr_obs_path;
+// DESIGN.md section 33)
+enum class FsrRoute
+{
+    None,           // not a format FrameIngest::Select knows
+    Planes420,      // the body of lvk_hip_fsr_yuv420: k_fsr_planes staged from the planes, or ingest into a pooled frame and its direct taps
+    FusedPlanes,    // k_fsr_planes<plane source, sink, staged>: one launch, planes to planes (4:2:2, 4:4:4, AYUV)
+    FusedPacked,    // ingest into a pooled frame -> k_fsr_planes<PackedYuv, sink, direct> into the planes
+    Bgr,            // lvk_hip_fsr_easu on three-byte pixels, plane to plane: BGR3 at its pitches, RGBA / BGRA / BGRX on the 3 * cols views
+    Gray            // lvk_hip_fsr_easu_gray, plane to plane
+};
+
+inline FsrRoute fsr_route(int vf, bool staged)
+{
+    if (is_420(vf)) return FsrRoute::Planes420;
+    if (vf == LVK_VIDEO_FORMAT_Y800) return FsrRoute::Gray;
+    if (vf == LVK_VIDEO_FORMAT_BGR3 || is_direct4(vf)) return FsrRoute::Bgr;
+    if (obs_rows(vf, 2).n == 0) return FsrRoute::None;
+    return staged ? FsrRoute::FusedPlanes : FsrRoute::FusedPacked;
 }
 
 // Where the luma bytes of a row of a fused format lie: the first at byte `first`, the next `stride` bytes on.  Planar Y planes: {0, 1}.

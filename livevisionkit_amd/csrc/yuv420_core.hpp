@@ -123,3 +123,6 @@ int lvk_scale_420(lvk_hip_ctx* ctx, const char* name, const yuv420::PlaneSet& sr
 
 // lvk::CASFilter on 4:2:0 planes (cas_420.hip): lvk_hip_cas_yuv420 behind its entry guard, shared with lvk_hip_cas_obs; `name` is the entry's
 int lvk_cas_420(lvk_hip_ctx* ctx, const char* name, const yuv420::PlaneSet& src, const yuv420::PlaneSet& dst, float sharpness);
+
+// lvk::FSRFilter on 4:2:0 planes (fsr_420.hip): lvk_hip_fsr_yuv420 behind its entry guard, shared with lvk_hip_fsr_obs; `name` is the entry's
+int lvk_fsr_420(lvk_hip_ctx* ctx, const char* name, const yuv420::PlaneSet& src, const int region_xywh[4], const yuv420::PlaneSet& dst);

@@ -2,15 +2,19 @@
 
 Frames are torch uint8 tensors [rows, cols, 3 | 4] on the GPU with contiguous rows (any row pitch: stride(1) == channels, stride(2) == 1).
 apply() works out of place on the context's stream; specification: tests/np_fsr.py and DESIGN.md section 16.  apply() also takes GRAY frames
-[rows, cols] (lvk_hip_fsr_easu_gray)."""
+[rows, cols] (lvk_hip_fsr_easu_gray).  apply_yuv420 takes the planes of an I420 / NV12 frame and writes new planes at the output size
+(lvk_hip_fsr_yuv420), apply_obs the planes of any OBS video format (lvk_hip_fsr_obs)."""
 import ctypes
 import math
 
 from . import _native
+from .context import _planes420_args, _planes420_empty
 from .stabilization import CHANNELS, FORMAT_BGR, FORMAT_GRAY, frame_args, gray_frame_args, out_frame
 
 _c = ctypes
 MAX_CROP = 4096
+_FORMATS_420 = (1, 2, 13)              # I420, NV12, I40A: even rows and cols
+_FORMATS_422 = (3, 4, 5, 12, 14)       # YVYU, YUY2, UYVY, I422, I42A: even cols
 
 
 def easu_const(rw, rh, W, H, ow, oh):
@@ -90,4 +94,70 @@ class FSRFilter:
         else:
             rc = self.lib.lvk_hip_fsr_easu(self.ctx.handle, src, src_step, rows, cols, int(fmt), reg, dst, dst_step, oh, ow)
         self.ctx._check(rc)
+        return out
+
+    @staticmethod
+    def _skipped(planes, out):
+        """A frame the geometry skips: the input planes themselves, or copied into `out`."""
+        if out is None:
+            return planes
+        for o, p in zip(out, planes):
+            if tuple(o.shape) != tuple(p.shape):
+                raise ValueError("out must have the shapes of the input planes")
+            o.copy_(p)
+        return out
+
+    def apply_yuv420(self, y, u, v=None, out=None):
+        """Scales the planes of an I420 (y [rows, cols], u, v [rows/2, cols/2]) or NV12 (v=None, u [rows/2, cols/2, 2]) frame OUT OF PLACE in one call
+        (lvk_hip_fsr_yuv420): byte for byte the ingest -> apply(FORMAT_YUV) -> egress chain.  `out` = the output planes in the same layout at the output
+        size (allocated when None; rows may be padded: stride(-1) == 1, NV12 UV stride(1) == 2).  An output size with an odd side raises ValueError.
+        Returns the output planes as a tuple; a frame the geometry skips comes back as the input planes (or copied into `out`).  Asynchronous on the
+        context's stream."""
+        nv12 = v is None
+        planes = (y, u) if nv12 else (y, u, v)
+        rows, cols = int(y.shape[0]), int(y.shape[1])
+        if out is not None:
+            out = tuple(out)
+            if len(out) != len(planes):
+                raise ValueError("`out` holds one plane per input plane")
+        region, (oh, ow), skip = self.geometry(rows, cols)
+        if skip:
+            return self._skipped(planes, out)
+        if (oh | ow) & 1:
+            raise ValueError("a 4:2:0 frame takes even sizes only: the output would be %d x %d" % (ow, oh))
+        out = _planes420_empty(oh, ow, nv12, y.device) if out is None else out
+        for group, (r, c) in ((planes, (rows, cols)), (out, (oh, ow))):
+            chroma = (r // 2, c // 2, 2) if nv12 else (r // 2, c // 2)
+            for p, shape in zip(group, ((r, c), chroma, chroma)):
+                if tuple(p.shape) != shape or p.dtype.itemsize != 1 or p.stride(-1) != 1 or (p.dim() == 3 and p.stride(1) != 2):
+                    raise ValueError("8-bit planes [rows, cols], [rows/2, cols/2] (NV12: [rows/2, cols/2, 2]) with contiguous rows are required")
+        self.ctx._check(self.lib.lvk_hip_fsr_yuv420(self.ctx.handle, *_planes420_args(planes, nv12), rows, cols, (_c.c_int * 4)(*region),
+                                                    *_planes420_args(out, nv12), oh, ow, 1 if nv12 else 0))
+        return out
+
+    def apply_obs(self, fmt, planes, out=None):
+        """Scales the planes of one frame of ANY OBS video format OUT OF PLACE in one call (lvk_hip_fsr_obs): byte for byte the
+        ctx.ingest_obs -> apply(the format's frame format) -> ctx.egress_obs chain.  `fmt` = a name of Context.VIDEO_FORMATS or its number; `planes`
+        as ctx.ingest_obs takes them; `out` = the planes of the output frame at the output size (allocated when None -- plane i is the input's plane i
+        at the new size; bytes the egress leaves alone are then undefined; rows may be padded).  An output size the format cannot take (an odd width on
+        4:2:2, an odd side on 4:2:0) raises ValueError.  Returns the output planes as a list; a frame the geometry skips comes back as the input planes
+        (or copied into `out`).  Asynchronous on the context's stream."""
+        import torch
+        planes = list(planes)
+        vf = self.ctx.video_format(fmt)
+        rows, cols = int(planes[0].shape[0]), int(planes[0].shape[1])
+        if out is not None:
+            out = list(out)
+            if len(out) != len(planes):
+                raise ValueError("`out` holds one plane per input plane")
+        region, (oh, ow), skip = self.geometry(rows, cols)
+        if skip:
+            return self._skipped(planes, out)
+        if (vf in _FORMATS_420 and (oh | ow) & 1) or (vf in _FORMATS_422 and ow & 1):
+            raise ValueError("video format %r does not take the output size %d x %d" % (fmt, ow, oh))
+        if out is None:
+            out = [torch.empty((p.shape[0] * oh // rows, p.shape[1] * ow // cols, *p.shape[2:]), dtype=torch.uint8, device=p.device) for p in planes]
+        iptr, istep = self.ctx._obs_args(planes)
+        optr, ostep = self.ctx._obs_args(out)
+        self.ctx._check(self.lib.lvk_hip_fsr_obs(self.ctx.handle, vf, iptr, istep, rows, cols, (_c.c_int * 4)(*region), optr, ostep, oh, ow))
         return out
