@@ -3,11 +3,11 @@
 // and DESIGN.md section 16.
 //
 // One kernel, k_fsr_easu<C, kStaged>, on the context's stream.  A block of 256 threads owns a 64 x 16 pixel output tile; lane l of wave w
-// computes column l of rows 4w .. 4w + 3.  The texel of a tap is (fp.x + rx + dx, fp.y + ry + dy), dx, dy in -1 .. 2, clamped to the frame:
-// the shader's point sampler picks exactly that texel (declared choice 6, pinned by tests/test_fsr_spec.py), so no texture coordinate is
-// formed here.  Two ways to fetch a tap, chosen per launch by the host from the scale:
+// computes column l of rows 4w .. 4w + 3.  The tile walk (which texel a tap is, the stage fill, the 12-tap gather) and the pixel function are
+// fsr_core.hpp's; this unit adds the texel of a packed pixel, the skip of the lanes beyond the row's end and the pixel store.  Two ways to
+// fetch a tap, chosen per launch by the host from the scale:
 //   staged   the tile's source footprint (its fp range plus the -1 .. 2 taps) is read once into LDS as float4 (r, g, b, luma): each texel
-//            is converted and its luma computed once, not once per tap.  Used when the largest footprint of the launch fits kStagePixels.
+//            is converted and its luma computed once, not once per tap.  Used when the largest footprint of the launch fits the stage.
 //   direct   each tap reads its bytes from the frame and computes its luma (downscales whose footprint does not fit).
 // The arithmetic is the specification's, unfused, with the FidelityFX bit tricks and a correctly rounded 1 / aW.  Output bytes are
 // stored one channel at a time (a whole dword for 4-channel pixels at an aligned address): no byte outside out_cols * C of a row is written.
@@ -20,20 +20,14 @@
 
 namespace {
 
-using namespace ffx;                       // the tile, the analysis, the taps, FsrEasuF on float4 texels, the byte conversions (fsr_core.hpp): shared with fsr_gray.hip and fsr_planes.hpp
-
-constexpr int kStagePixels = 2560;         // LDS budget of the staged path: 40 KiB of float4, four blocks per CU
+using namespace ffx;                       // the tile and its walk, FsrEasuF on float4 texels, the byte conversions, the host's prelude (fsr_core.hpp)
 
 struct EasuArgs
 {
     const uint8_t* src;
     long long src_step;
-    int rows, cols;                        // the frame
-    int rx, ry;                            // the region's origin
     uint8_t* dst;
     long long dst_step;
-    int out_rows, out_cols;
-    float c0x, c0y, c0z, c0w;              // FsrEasuCon's con0 (con1 .. con3 only place the texels, which are integers here)
     int ri, bi;                            // byte of the shader's r and b (g is byte 1)
 };
 
@@ -62,76 +56,29 @@ __device__ __forceinline__ void store_pixel(const EasuArgs& a, int x, int y, flo
 
 template <int C, bool kStaged>
 __global__ __launch_bounds__(256)
-void k_fsr_easu(EasuArgs a)
+void k_fsr_easu(EasuArgs a, FsrGeo g)
 {
-    __shared__ float4 stage[kStaged ? kStagePixels : 1];
+    __shared__ float4 stage[kStaged ? kStageTexels<float4> : 1];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x0 = blockIdx.x * kTileW;
     const int x = x0 + lane;
-    const float ppx_full = pp_of(x, a.c0x, a.c0z);
-    const float fpx = floorf(ppx_full), ppx = ppx_full - fpx;
-    const int fx = (int)fpx;
-    // the tile's first and last fp.x: pp grows with x, and rounding keeps that order
-    const int fx0 = (int)floorf(pp_of(x0, a.c0x, a.c0z));
-    const int fx1 = (int)floorf(pp_of(min(x0 + kTileW, a.out_cols) - 1, a.c0x, a.c0z));
-    const int sw = fx1 - fx0 + 4;                                  // staged columns: fp.x - 1 .. fp.x + 2
+    const EasuCol col = easu_col(g, x0, x);
+    const auto fetch = [&](int sx, int sy) { return texel(a.src + (long long)sy * a.src_step + (long long)sx * C, a.ri, a.bi); };
 
-    for (int y0 = blockIdx.y * kTileH; y0 < a.out_rows; y0 += gridDim.y * kTileH)
+    for (int y0 = blockIdx.y * kTileH; y0 < g.out_rows; y0 += gridDim.y * kTileH)
     {
-        int fy0 = 0;
-        if (kStaged)
-        {
-            fy0 = (int)floorf(pp_of(y0, a.c0y, a.c0w));
-            const int fy1 = (int)floorf(pp_of(min(y0 + kTileH, a.out_rows) - 1, a.c0y, a.c0w));
-            const int sh = fy1 - fy0 + 4;
-            for (int k = tid; k < sw * sh; k += 256)
-            {
-                const int ty = k / sw, tx = k - ty * sw;
-                const int sx = min(max(fx0 - 1 + a.rx + tx, 0), a.cols - 1);
-                const int sy = min(max(fy0 - 1 + a.ry + ty, 0), a.rows - 1);
-                stage[k] = texel(a.src + (long long)sy * a.src_step + (long long)sx * C, a.ri, a.bi);
-            }
-            __syncthreads();
-        }
-        if (x < a.out_cols)
+        const int fy0 = kStaged ? easu_stage_fill(stage, g, col, y0, tid, fetch) : 0;
+        if (x < g.out_cols)
         {
 #pragma unroll 1
             for (int j = 0; j < kRowsPerWave; j++)
             {
                 const int y = y0 + wave * kRowsPerWave + j;
-                if (y >= a.out_rows) break;
-                const float ppy_full = pp_of(y, a.c0y, a.c0w);
-                const float fpy = floorf(ppy_full), ppy = ppy_full - fpy;
-                const int fy = (int)fpy;
+                if (y >= g.out_rows) break;
                 float4 t[4][4];
-                if (kStaged)
-                {
-                    const float4* s = stage + (fy - fy0) * sw + (fx - fx0);
-#pragma unroll
-                    for (int dy = 0; dy < 4; dy++)
-#pragma unroll
-                        for (int dx = 0; dx < 4; dx++)
-                            if ((dy == 0 || dy == 3) && (dx == 0 || dx == 3)) t[dy][dx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                            else t[dy][dx] = s[dy * sw + dx];
-                }
-                else
-                {
-                    int cx[4];
-#pragma unroll
-                    for (int dx = 0; dx < 4; dx++) cx[dx] = min(max(fx + a.rx + dx - 1, 0), a.cols - 1);
-#pragma unroll
-                    for (int dy = 0; dy < 4; dy++)
-                    {
-                        const int sy = min(max(fy + a.ry + dy - 1, 0), a.rows - 1);
-                        const uint8_t* row = a.src + (long long)sy * a.src_step;
-#pragma unroll
-                        for (int dx = 0; dx < 4; dx++)
-                            if ((dy == 0 || dy == 3) && (dx == 0 || dx == 3)) t[dy][dx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                            else t[dy][dx] = texel(row + (long long)cx[dx] * C, a.ri, a.bi);
-                    }
-                }
-                store_pixel<C>(a, x, y, easu(t, ppx, ppy));
+                const float ppy = easu_gather<kStaged>(t, stage, g, col, fy0, y, fetch);
+                store_pixel<C>(a, x, y, easu(t, col.ppx, ppy));
             }
         }
         if (kStaged) __syncthreads();                               // the stage is reused by the next row of tiles
@@ -160,10 +107,7 @@ int lvk_hip_fsr_easu_const(int rw, int rh, int W, int H, int ow, int oh, float c
 
 int lvk_hip_fsr_easu_path(int rw, int rh, int out_rows, int out_cols)
 {
-    float con[16];
-    if (lvk_hip_fsr_easu_const(rw, rh, 1, 1, out_cols, out_rows, con) != LVK_HIP_OK) return LVK_HIP_ERR_ARG;
-    const long long sw = max_fp_span(out_cols, kTileW, con[0], con[2]) + 3LL, sh = max_fp_span(out_rows, kTileH, con[1], con[3]) + 3LL;
-    return sw * sh <= kStagePixels ? 0 : 1;
+    return fsr_stage_fits(rw, rh, out_rows, out_cols, kStageTexels<float4>);
 }
 
 int lvk_hip_fsr_geometry(int rows, int cols, int out_rows, int out_cols, float multiplier, int maintain_aspect_ratio, const int crop_ltrb[4],
@@ -204,29 +148,26 @@ int lvk_hip_fsr_easu(lvk_hip_ctx* ctx, const void* d_src, int src_step, int rows
     const int ch = lvk_format_channels(format);
     if (ch != 3 && ch != 4) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: packed BGR / RGB / YUV / BGRA / RGBA frames only");
     LVK_HIP_REQUIRE(ctx, d_src && d_dst && region_xywh && rows > 0 && cols > 0 && out_rows > 0 && out_cols > 0);
-    const int rx = region_xywh[0], ry = region_xywh[1], rw = region_xywh[2], rh = region_xywh[3];
-    if (!(rx >= 0 && ry >= 0 && rw > 0 && rh > 0 && (long long)rx + rw <= cols && (long long)ry + rh <= rows))
+    if (!fsr_region_ok(region_xywh, rows, cols))
         return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: the region must be a non-empty rectangle inside the frame");
     const long long src_row = (long long)cols * ch, dst_row = (long long)out_cols * ch;
     LVK_HIP_REQUIRE(ctx, (long long)src_step >= src_row && (long long)dst_step >= dst_row);
     if (lvk_pitched_overlap(d_src, src_step, rows, src_row, d_dst, dst_step, out_rows, dst_row)) return ctx->fail(LVK_HIP_ERR_ARG, "lvk_hip_fsr_easu: the source and destination overlap");
 
-    float con[16];
-    lvk_hip_fsr_easu_const(rw, rh, cols, rows, out_cols, out_rows, con);
     const bool bgr = format == LVK_FORMAT_BGR || format == LVK_FORMAT_BGRA;
-    const EasuArgs a{(const uint8_t*)d_src, (long long)src_step, rows, cols, rx, ry, (uint8_t*)d_dst, (long long)dst_step, out_rows, out_cols,
-                     con[0], con[1], con[2], con[3], bgr ? 2 : 0, bgr ? 0 : 2};
-    const bool staged = lvk_hip_fsr_easu_path(rw, rh, out_rows, out_cols) == 0;
-    const dim3 grid((unsigned)((out_cols + kTileW - 1) / kTileW), (unsigned)std::min((out_rows + kTileH - 1) / kTileH, 65535));
+    const EasuArgs a{(const uint8_t*)d_src, (long long)src_step, (uint8_t*)d_dst, (long long)dst_step, bgr ? 2 : 0, bgr ? 0 : 2};
+    const FsrGeo geo = fsr_geo(rows, cols, region_xywh, out_rows, out_cols);
+    const bool staged = lvk_hip_fsr_easu_path(region_xywh[2], region_xywh[3], out_rows, out_cols) == 0;
+    const dim3 grid = fsr_grid(geo);
     if (ch == 3)
     {
-        if (staged) hipLaunchKernelGGL((k_fsr_easu<3, true>), grid, dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_fsr_easu<3, false>), grid, dim3(256), 0, ctx->stream, a);
+        if (staged) hipLaunchKernelGGL((k_fsr_easu<3, true>), grid, dim3(256), 0, ctx->stream, a, geo);
+        else hipLaunchKernelGGL((k_fsr_easu<3, false>), grid, dim3(256), 0, ctx->stream, a, geo);
     }
     else
     {
-        if (staged) hipLaunchKernelGGL((k_fsr_easu<4, true>), grid, dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_fsr_easu<4, false>), grid, dim3(256), 0, ctx->stream, a);
+        if (staged) hipLaunchKernelGGL((k_fsr_easu<4, true>), grid, dim3(256), 0, ctx->stream, a, geo);
+        else hipLaunchKernelGGL((k_fsr_easu<4, false>), grid, dim3(256), 0, ctx->stream, a, geo);
     }
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;

@@ -5,7 +5,7 @@
 //   staged   Src420 -- the planes themselves, up-sampled into the LDS stage: ONE launch, no packed frame at all
 //   direct   PackedYuv -- lvk_launch_ingest_yuv420 into a frame from the context's pool, which goes back to the pool inside the call (whoever is handed
 //            it next enqueues behind this kernel on the context's stream), then the taps read that frame
-// chosen by lvk_hip_fsr_obs_path, the one place that knows the stage's budget.
+// chosen by lvk_hip_fsr_obs_path: fsr_stage_fits (fsr_core.hpp) against the stage of float4 texels.
 #include "lvk_hip_internal.hpp"
 #include "fsr_planes.hpp"
 
@@ -13,10 +13,7 @@ using namespace yuv420;
 
 extern "C" int lvk_hip_fsr_obs_path(int rw, int rh, int out_rows, int out_cols)
 {
-    float con[16];
-    if (lvk_hip_fsr_easu_const(rw, rh, 1, 1, out_cols, out_rows, con) != LVK_HIP_OK) return LVK_HIP_ERR_ARG;
-    const long long sw = max_fp_span(out_cols, kTileW, con[0], con[2]) + 3LL, sh = max_fp_span(out_rows, kTileH, con[1], con[3]) + 3LL;
-    return sw * sh <= kFsrStagePixels ? 0 : 1;
+    return fsr_stage_fits(rw, rh, out_rows, out_cols, kStageTexels<float4>);
 }
 
 // lvk_hip_fsr_yuv420 behind its entry guard: also the I420 / I40A / NV12 route of lvk_hip_fsr_obs (fsr_obs.hip)

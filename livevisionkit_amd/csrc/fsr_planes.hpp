@@ -1,19 +1,19 @@
 // The FSR 1 EASU pass on the PLANES of an OBS video format (lvk_hip_fsr_yuv420: fsr_420.hip; lvk_hip_fsr_obs: fsr_obs.hip): the one
 // kernel body both units instantiate, its launch, and what the two entries check alike.  The output planes are byte for byte those of
 //   ingest -> lvk_hip_fsr_easu(format = YUV) -> egress
-// so the kernel is k_fsr_easu<3, .> of fsr.hip (same tile, same arithmetic: easu of fsr_core.hpp on texels (Y, U, V, luma), luma = 0.5 V + (0.5 Y + U))
-// with the ingest in front of its taps and the egress behind its pixels:
+// so the kernel stands on what k_fsr_easu<3, .> of fsr.hip stands on (the tile walk and easu of fsr_core.hpp, on texels (Y, U, V, luma), luma =
+// 0.5 V + (0.5 Y + U)) with the ingest in front of its taps and the egress behind its pixels:
 //   Src    px(sx, sy): the packed pixel 0x00VVUUYY the ingest writes at (sx, sy) of the frame, formed from the planes -- the chroma UP-SAMPLED by the
 //          ingest's closed forms at FRAME coordinates, so a region at an odd origin reads the other chroma phase.  sx, sy are clamped into the frame
 //          first (the point sampler's clamp), then the chroma phase is taken; the up-sampling clamps its own far sample (the edge replicated).
 //   staged the tile's source footprint goes through Src once into LDS as float4: the ONE place the planes are read; a texel is converted once
-//   direct the taps read a packed 8UC3 frame (PackedYuv: the pooled frame the ingest kernels made) with clamped indices, as k_fsr_easu<3, false> does
+//   direct the taps read a packed 8UC3 frame (PackedYuv: the pooled frame the ingest kernels made) with clamped indices
 //   Out    the sinks take four horizontally adjacent pixels (obs_sinks.hpp), the 4:2:0 stores four columns of a row pair (yuv420_core.hpp), while a
 //          thread of the tile computes a COLUMN of four rows.  So every thread puts its four pixels as 0x00VVUUYY into an LDS out-tile of 16 x 64
 //          words, and after a barrier the threads read it back in the output's shape: the quad mean (sum + 2) >> 2 of 4:2:0 and the pair sum halved
 //          half-to-even of 4:2:2 are taken there, on the scaled full-resolution chroma, as the egress takes them.  Both tile sides are even and the
 //          width a multiple of 4: no quad, pair or group of four straddles two tiles.  The out-tile aliases the first 4 KiB of the stage (a barrier
-//          after the last tap), so the stage keeps fsr.hip's 2560 texels = 40 KiB and four blocks fit a CU.
+//          after the last tap), so the stage keeps the 40 KiB of every EASU kernel and four blocks fit a CU.
 // No load touches a byte outside the used bytes of a plane row, and no store one outside those of an output row.
 #pragma once
 
@@ -27,16 +27,7 @@ namespace {
 
 using namespace ffx;
 
-constexpr int kFsrStagePixels = 2560;                  // LDS budget of the staged path: 40 KiB of float4 (lvk_hip_fsr_obs_path)
 constexpr int kFsrOutWords = kTileW * kTileH;          // the out-tile: 4 KiB, inside the stage
-
-struct FsrGeo
-{
-    int rows, cols;                        // the frame
-    int rx, ry;                            // the region's origin
-    int out_rows, out_cols;
-    float c0x, c0y, c0z, c0w;              // FsrEasuCon's con0
-};
 
 // (Y, U, V, luma) of a packed pixel 0x00VVUUYY: texel() of fsr.hip with r, g, b = bytes 0, 1, 2
 __device__ __forceinline__ float4 yuv_texel(uint32_t px)
@@ -110,37 +101,18 @@ template <class Src, class Out, bool kStaged>
 __global__ __launch_bounds__(256)
 void k_fsr_planes(Src src, Out out, FsrGeo a)
 {
-    __shared__ float4 stage[kStaged ? kFsrStagePixels : kFsrOutWords / 4];
+    __shared__ float4 stage[kStaged ? kStageTexels<float4> : kFsrOutWords / 4];
     float* tile = reinterpret_cast<float*>(stage);                 // the out-tile: words carried as floats, bits untouched
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x0 = blockIdx.x * kTileW;
     const int x = x0 + lane;
-    const float ppx_full = pp_of(x, a.c0x, a.c0z);
-    const float fpx = floorf(ppx_full), ppx = ppx_full - fpx;
-    const int fx = (int)fpx;
-    // the tile's first and last fp.x: pp grows with x, and rounding keeps that order
-    const int fx0 = (int)floorf(pp_of(x0, a.c0x, a.c0z));
-    const int fx1 = (int)floorf(pp_of(min(x0 + kTileW, a.out_cols) - 1, a.c0x, a.c0z));
-    const int sw = fx1 - fx0 + 4;                                  // staged columns: fp.x - 1 .. fp.x + 2
+    const EasuCol col = easu_col(a, x0, x);
+    const auto fetch = [&](int sx, int sy) { return yuv_texel(src.px(sx, sy)); };
 
     for (int y0 = blockIdx.y * kTileH; y0 < a.out_rows; y0 += gridDim.y * kTileH)
     {
-        int fy0 = 0;
-        if (kStaged)
-        {
-            fy0 = (int)floorf(pp_of(y0, a.c0y, a.c0w));
-            const int fy1 = (int)floorf(pp_of(min(y0 + kTileH, a.out_rows) - 1, a.c0y, a.c0w));
-            const int sh = fy1 - fy0 + 4;
-            for (int k = tid; k < sw * sh; k += 256)
-            {
-                const int ty = k / sw, tx = k - ty * sw;
-                const int sx = min(max(fx0 - 1 + a.rx + tx, 0), a.cols - 1);
-                const int sy = min(max(fy0 - 1 + a.ry + ty, 0), a.rows - 1);
-                stage[k] = yuv_texel(src.px(sx, sy));
-            }
-            __syncthreads();
-        }
+        const int fy0 = kStaged ? easu_stage_fill(stage, a, col, y0, tid, fetch) : 0;
         uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;                    // the thread's column of four pixels
         if (x < a.out_cols)
         {
@@ -149,43 +121,16 @@ void k_fsr_planes(Src src, Out out, FsrGeo a)
             {
                 const int y = y0 + wave * kRowsPerWave + j;
                 if (y >= a.out_rows) break;
-                const float ppy_full = pp_of(y, a.c0y, a.c0w);
-                const float fpy = floorf(ppy_full), ppy = ppy_full - fpy;
-                const int fy = (int)fpy;
                 float4 t[4][4];
-                if (kStaged)
-                {
-                    const float4* s = stage + (fy - fy0) * sw + (fx - fx0);
-#pragma unroll
-                    for (int dy = 0; dy < 4; dy++)
-#pragma unroll
-                        for (int dx = 0; dx < 4; dx++)
-                            if ((dy == 0 || dy == 3) && (dx == 0 || dx == 3)) t[dy][dx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                            else t[dy][dx] = s[dy * sw + dx];
-                }
-                else
-                {
-                    int cx[4];
-#pragma unroll
-                    for (int dx = 0; dx < 4; dx++) cx[dx] = min(max(fx + a.rx + dx - 1, 0), a.cols - 1);
-#pragma unroll
-                    for (int dy = 0; dy < 4; dy++)
-                    {
-                        const int sy = min(max(fy + a.ry + dy - 1, 0), a.rows - 1);
-#pragma unroll
-                        for (int dx = 0; dx < 4; dx++)
-                            if ((dy == 0 || dy == 3) && (dx == 0 || dx == 3)) t[dy][dx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                            else t[dy][dx] = yuv_texel(src.px(cx[dx], sy));
-                    }
-                }
-                const float3 pix = easu(t, ppx, ppy);
+                const float ppy = easu_gather<kStaged>(t, stage, a, col, fy0, y, fetch);
+                const float3 pix = easu(t, col.ppx, ppy);
                 const uint32_t w = to_byte(pix.x) | (to_byte(pix.y) << 8) | (to_byte(pix.z) << 16);
                 o0 = j == 0 ? w : o0; o1 = j == 1 ? w : o1; o2 = j == 2 ? w : o2; o3 = j == 3 ? w : o3;      // no indexed array: no scratch
             }
         }
         if (kStaged) __syncthreads();                               // every tap is read: the out-tile takes the stage's first words
-        float* col = tile + wave * kRowsPerWave * kTileW + lane;
-        col[0] = as_f(o0); col[kTileW] = as_f(o1); col[2 * kTileW] = as_f(o2); col[3 * kTileW] = as_f(o3);
+        float* out_col = tile + wave * kRowsPerWave * kTileW + lane;
+        out_col[0] = as_f(o0); out_col[kTileW] = as_f(o1); out_col[2 * kTileW] = as_f(o2); out_col[3 * kTileW] = as_f(o3);
         __syncthreads();
         out.store_tile(tile, x0, y0, a.out_rows, a.out_cols, tid);
         __syncthreads();                                            // the tile and the stage are reused by the next row of tiles
@@ -195,24 +140,9 @@ void k_fsr_planes(Src src, Out out, FsrGeo a)
 template <class Src, class Out, bool kStaged>
 int launch_fsr_planes(lvk_hip_ctx* ctx, const Src& src, const Out& out, const FsrGeo& a)
 {
-    const dim3 grid((unsigned)((a.out_cols + kTileW - 1) / kTileW), (unsigned)std::min((a.out_rows + kTileH - 1) / kTileH, 65535));
-    hipLaunchKernelGGL((k_fsr_planes<Src, Out, kStaged>), grid, dim3(256), 0, ctx->stream, src, out, a);
+    hipLaunchKernelGGL((k_fsr_planes<Src, Out, kStaged>), fsr_grid(a), dim3(256), 0, ctx->stream, src, out, a);
     LVK_HIP_CHECK(ctx, hipGetLastError());
     return LVK_HIP_OK;
-}
-
-// what lvk_hip_fsr_easu asks of its region and output size
-inline bool fsr_region_ok(const int region_xywh[4], int rows, int cols)
-{
-    const int rx = region_xywh[0], ry = region_xywh[1], rw = region_xywh[2], rh = region_xywh[3];
-    return rx >= 0 && ry >= 0 && rw > 0 && rh > 0 && (long long)rx + rw <= cols && (long long)ry + rh <= rows;
-}
-
-inline FsrGeo fsr_geo(int rows, int cols, const int region_xywh[4], int out_rows, int out_cols)
-{
-    float con[16];
-    lvk_hip_fsr_easu_const(region_xywh[2], region_xywh[3], cols, rows, out_cols, out_rows, con);
-    return FsrGeo{rows, cols, region_xywh[0], region_xywh[1], out_rows, out_cols, con[0], con[1], con[2], con[3]};
 }
 
 // the packed frame of the direct route: its pitch (rows on a dword, where the ingest kernels take their wide stores)

@@ -301,6 +301,40 @@ def test_two_filters_on_one_context(ctx):
     assert all(np.array_equal(g.cpu().numpy(), w) for g, w in zip(a.apply_obs("YUY2", pa), expected(cc)["want"]))
 
 
+# (frame rows, cols), region or None, (output rows, cols), the path of the float4 stages (packed, planes), the path of the float stage (gray)
+FAMILY_CASES = [((38, 70), (3, 1, 61, 33), (37, 131), STAGED, STAGED),     # partial last tiles in both axes
+                ((38, 70), None, (5, 9), STAGED, STAGED),                  # a footprint of nearly the whole frame: 66 x 34 texels still fit
+                ((38, 70), None, (16, 64), DIRECT, STAGED),                # one full tile over the whole frame: 72 x 39 float4 texels do not
+                ((110, 110), None, (16, 64), DIRECT, DIRECT)]              # ... and 111 x 106 fit neither stage
+
+
+def test_the_three_kernel_families_agree_on_one_frame(ctx):
+    """The packed, the plane and the one-channel kernels walk their tiles with the same code (csrc/fsr_core.hpp): on one frame, lvk_hip_fsr_easu(YUV)
+    on the packed pixels equals lvk_hip_fsr_obs(I444) on its three planes byte for byte, and lvk_hip_fsr_easu_gray on plane g equals channel 0 of
+    lvk_hip_fsr_easu(BGR) on (g, g, g) (the definition of DESIGN.md section 24), on the staged and on the direct path of each."""
+    import torch
+    import livevisionkit_amd as lvk
+    for (rows, cols), region, dst, path4, path1 in FAMILY_CASES:
+        rx, ry, rw, rh = region or (0, 0, cols, rows)
+        what = ((rows, cols), region, dst)
+        assert ctx.lib.lvk_hip_fsr_easu_path(rw, rh, *dst) == ctx.lib.lvk_hip_fsr_obs_path(rw, rh, *dst) == path4, what
+        assert ctx.lib.lvk_hip_fsr_easu_gray_path(rw, rh, *dst) == path1, what
+        f = lvk.FSRFilter(ctx, output_size=dst, maintain_aspect_ratio=False, crop=(rx, ry, cols - rx - rw, rows - ry - rh))
+        assert tuple(f.geometry(rows, cols)[0]) == (rx, ry, rw, rh), what
+        frame = gpu(np.random.default_rng(38).integers(0, 256, (rows, cols, 3), dtype=np.uint8))
+        planes = [frame[..., c].contiguous() for c in range(3)]
+        packed = f.apply(frame, FORMAT_YUV)
+        by_planes = f.apply_obs("I444", planes)
+        g = planes[0]
+        gray = f.apply(g)
+        bgr = f.apply(torch.stack([g, g, g], dim=2), FORMAT_BGR)
+        ctx.sync()
+        assert tuple(packed.shape) == dst + (3,) and tuple(gray.shape) == dst, what
+        for c in range(3):
+            assert torch.equal(packed[..., c], by_planes[c]), (what, c)
+        assert torch.equal(gray, bgr[..., 0]), what
+
+
 @pytest.mark.parametrize("fmt", CROP_FORMATS)
 def test_the_python_methods_forms(ctx, fmt):
     """The crop settings of the filter reach the entry as the region ((7, 5, 9, 11) of a 24 x 40 frame: crop 7, 5, 24, 8); a skipped frame comes back as it
